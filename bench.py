@@ -7,10 +7,13 @@ kernels) + RCCL gradient all-reduce (N>1, the library's vitmi_comm_* leg on a si
 overlapped with the backward) + Keras Adam update (one fused vitmi launch), on a synthetic
 batch of 256 images/GPU already resident in HBM, random-init ViT-B/16 weights.
 
-Launch:  python bench.py [--gpus 1 --steps 10 --warmup 3]
+Launch:  python bench.py [--gpus 1 --steps 10 --warmup 3] [--dump-outputs DIR] [--full]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
              --master-port P bench.py --gpus N ...
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries, measured in this run:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times `--steps` steps and prints the
+line (contract fields, `ms_per_step`, the phases' GPU times and the fc1 GEMM's HIP-event time, all
+taken inside the timed region).  --dump-outputs DIR also writes what the last timed step computed
+(dump_outputs below).  With --full the line carries in addition, measured in this run:
   roofline      the dominant kernel (fc1 GEMM [M x 3072 x 768] + bias + GELU) timed with HIP
                 events on its stream inside the timed region; `traffic` = its HBM bytes per
                 launch from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over the same
@@ -22,7 +25,8 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries, measured i
   parity        this line's own arithmetic (dtype, knobs) against the north star's 1e-3: logits
                 max-abs of the line's full-depth model with randomised parameters on 2 images
                 vs the fp32 CPU oracle (every line, secondary ones included).
-The evidence legs run after the timed region (N=1, rank 0) and never change `value`.
+The --full legs run after the timed region (N=1, rank 0) and never change `value`; each has its
+own --no-* switch.
 """
 from __future__ import annotations
 
@@ -325,6 +329,15 @@ def main():
                     help="dtype of the gradient all-reduce (bf16 halves the bytes; vitmi comm only)")
     ap.add_argument("--reserve-cus", type=int, default=0,
                     help="CUs the persistent GEMM leaves to RCCL while buckets are in flight (N>1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the legs that take runs of their own: the logits "
+                         "check against the fp32 CPU oracle (parity), the CPU baseline, the rocprofv3 traffic "
+                         "and per-kernel legs and the secondary lines (each has a --no-* switch below); a run "
+                         "without --full measures the headline figure alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                         "(float32): logits, loss, and a fixed seeded sample of the gradients and of the "
+                         "updated parameters; the inputs are the same from run to run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true",
                     help="skip the line's logits check against the fp32 CPU oracle (after the timed region)")
@@ -347,6 +360,8 @@ def main():
     ap.add_argument("--comm-timeout", type=float, default=600.0,
                     help="seconds before a hung gradient exchange aborts the RCCL communicator (0: off)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_parity = args.no_cpu_baseline = args.no_evidence = args.no_secondary = True
 
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     # with the vitmi communicator the process group only bootstraps (rendezvous, TCPStore,
@@ -414,6 +429,7 @@ def main():
 
     phase_events = []   # per timed step: events between the phases (GPU time of each, compute stream)
     phases = ("forward", "backward", "allreduce_wait", "optimizer")
+    last = {}           # the last step's logits (what --dump-outputs writes)
 
     def step(timed=False):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timed else None
@@ -425,6 +441,7 @@ def main():
         with trace.range("vitmi:forward"):
             logits = model(img)
             loss = cross_entropy(logits, tgt)
+        last["logits"] = logits.detach()
         if timed:
             ev[1].record()
         with trace.range("vitmi:backward"):
@@ -474,6 +491,9 @@ def main():
         _dump_stats(args.stats_out)
     if comm is not None:
         comm.check()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["logits"], loss, arena)
+    last.clear()
     t = torch.tensor([elapsed], dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -566,6 +586,29 @@ def main():
         dist.destroy_process_group()
 
 
+DUMP_SAMPLE = 1 << 21       # elements of each flat buffer that --dump-outputs keeps (8 MiB as fp32)
+
+
+def dump_outputs(path, logits, loss, arena):
+    """What the last timed step handed back, as float32 `<name>.npy` under `path`: the logits
+    [B, classes], the loss, and the step's effect on the model: the gradients it left in the arena
+    and the parameters after its optimizer update.  Buffers larger than DUMP_SAMPLE elements are
+    written as a fixed sample (sorted indices drawn without replacement from numpy's
+    default_rng(0), which depend on the buffer's length alone), so two builds write the same
+    elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "logits.npy"), logits.detach().float().cpu().numpy())
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+    for name, buf in (("grads", arena.grad), ("params", arena.flat)):
+        n = buf.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+            buf = buf[torch.from_numpy(idx).to(buf.device)]
+            name += "_sample"
+        np.save(os.path.join(path, name + ".npy"), buf.detach().float().cpu().numpy())
+
+
 def secondary_lines():
     """The precision knob's C3 lines and BASELINE configs 5 (ViT-L/16 384px bs 64, N = 577) and 2
     (ViT-S/16 224px bs 128 fp32) on the driver's clock: child runs of this bench after the headline;
@@ -588,8 +631,8 @@ def secondary_lines():
             "c3_fp32": ["--config", "c3", "--dtype", "fp32", "--steps", "3", "--warmup", "1"]}
     for cfg, extra in runs.items():
         log = os.path.join(tempfile.gettempdir(), f"vitmi_secondary_{cfg}.log")
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *extra, "--no-evidence", "--no-cpu-baseline",
-               "--no-secondary"]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *extra, "--full", "--no-evidence",
+               "--no-cpu-baseline", "--no-secondary"]
         rc = _run(cmd, 300, log=log)
         line = None
         if rc == 0:

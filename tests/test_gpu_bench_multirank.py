@@ -30,7 +30,7 @@ def test_bench_two_ranks_gloo_leg():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--comm", "gloo", "--steps", "2", "--warmup", "1", "--batch", "8",
-           "--no-evidence", "--no-cpu-baseline", "--no-secondary"]
+           "--full", "--no-evidence", "--no-cpu-baseline", "--no-secondary"]   # --full: the parity leg
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

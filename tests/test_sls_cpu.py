@@ -1,8 +1,8 @@
 """SLS data pipeline host logic vs oracle/sls_ref.py: the reference's
 valid-piece / label / process-parameter logic (models/CvT(Par).py:363-412), StandardScaler
 (pinned against scikit-learn), the train/val split (:437-453), the cv2 INTER_LINEAR axis
-tables (host half of the GPU resize), and the workbook reader on the reference's own
-workbooks when /root/reference is present (read in place, never copied; skipped elsewhere)."""
+tables (host half of the GPU resize), and the workbook reader on stored workbooks in the
+layout of the reference's own (tests/golden/sls_excel, written by tests/golden/gen_sls_workbooks.py)."""
 import math
 import os
 
@@ -13,8 +13,7 @@ from oracle import sls_ref
 from vitmi import sls
 from vitmi.xlsx import read_xlsx
 
-REF_EXCEL = "/root/reference/Excel"
-have_ref = pytest.mark.skipif(not os.path.isdir(REF_EXCEL), reason="reference workbooks absent")
+REF_EXCEL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sls_excel")
 
 
 def random_tables(seed, groups=12, per=5, nan_frac=0.15):
@@ -67,7 +66,6 @@ def test_layer_paths_follow_reference_layout():
     assert p[5] == "/d/circle(340x345)/trail40_05/layer_02.jpg"
 
 
-@have_ref
 def test_reference_workbooks():
     s = read_xlsx(os.path.join(REF_EXCEL, "Processed_Circle_test.xlsx"))
     assert s.nrows == 200 and s.header[0] == "Unnamed: 0"

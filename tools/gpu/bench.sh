@@ -5,6 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 export PYTHONUNBUFFERED=1 TMPDIR=/tmp
 R=$PWD
 tag=${1:-cur}; shift
+set -- --full "$@"      # the evidence legs (both runs below switch off the ones they do not want)
 mkdir -p gpurun_out/$tag
 timeout -k 10 600 python3 bench.py "$@" > gpurun_out/$tag/bench.json 2> gpurun_out/$tag/bench.err && \
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/$tag/prof -o run --output-format csv -- \
