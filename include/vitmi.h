@@ -398,6 +398,42 @@ int vitmi_dense_f32_bwd(int M, int N, int K, const float* dy, int64_t lddy, cons
 int vitmi_adam_step(int64_t n, float* p, const float* g, float* m, float* v, void* p_lp, float alpha, double beta_1,
                     double beta_2, float epsilon, float grad_scale, vitmi_stream_t stream);
 
+/* Global-norm clipping, decoupled weight decay and non-finite step skipping for the Adam step
+ * (keras.optimizers.Adam(global_clipnorm=, weight_decay=)), decided on the device: no host read.
+ *
+ * vitmi_grad_sumsq: partials[c] = sum of (double)g[i]^2 over chunk c = [c CHUNK, min(n, (c+1) CHUNK)),
+ *   CHUNK = VITMI_GRAD_SUMSQ_CHUNK elements; vitmi_grad_sumsq_partials(n) = ceil(n / CHUNK) doubles.
+ *   Each element is widened to fp64 before squaring (exact), every addition is fp64, in an order
+ *   fixed by the chunk alone (per thread, wave64 cross-lane, one fold through LDS; no atomics): a
+ *   partial does not depend on n, the grid or the device, so results are bitwise reproducible.
+ *   One streaming read of g (16-B loads; g 16-byte aligned, any n), one block per chunk.
+ *   CHUNK = 8192 (32 KiB of loads in flight per block; see DESIGN.md for the measurement).
+ * vitmi_clip_finalize: one block folds partials[0 .. n_partials) (thread t takes t, t + 256, ...
+ *   in ascending order, then the same fixed tree) and writes the 16-byte device record
+ *     struct { float coef; float norm; uint32_t skip; uint32_t skipped_total; }
+ *   norm = (float)(|grad_scale| sqrt(total));  coef = norm > clip_norm ? clip_norm / norm : 1.0f
+ *   (one fp32 division; exactly 1 when nothing is clipped; clip_norm == 0: off, coef = 1);
+ *   skip = skip_nonfinite && !isfinite(total);  skipped_total += skip.  A non-finite total gives
+ *   coef = NaN: without skip_nonfinite the NaN reaches every parameter, as in Keras.  The caller
+ *   zeroes the record once.  partials 8-byte, ctl 16-byte aligned; clip_norm >= 0.
+ * vitmi_adam_step_ctl: vitmi_adam_step (same rounded fp32 ops, same order) with
+ *   g' = (g * grad_scale) * coef        (the second product only if coef != 1; coef from ctl)
+ *   p  = p - (p * weight_decay) * lr    before the update, if weight_decay != 0 and the element's
+ *        64-element group has its byte of decay_mask set (ceil(n / 64) bytes; NULL: every group)
+ *   and, if ctl->skip, p, m and v left bit for bit as they were (p_lp is still written as
+ *   bf16(p)).  ctl == NULL: coef 1, never skipped.  With ctl == NULL and weight_decay == 0 the
+ *   results equal vitmi_adam_step's bitwise.  weight_decay >= 0; ctl 16-byte aligned. */
+#ifndef VITMI_GRAD_SUMSQ_CHUNK
+#define VITMI_GRAD_SUMSQ_CHUNK 8192
+#endif
+size_t vitmi_grad_sumsq_partials(int64_t n);
+int vitmi_grad_sumsq(int64_t n, const float* g, double* partials, vitmi_stream_t stream);
+int vitmi_clip_finalize(int64_t n_partials, const double* partials, float grad_scale, float clip_norm,
+                        int skip_nonfinite, void* ctl, vitmi_stream_t stream);
+int vitmi_adam_step_ctl(int64_t n, float* p, const float* g, float* m, float* v, void* p_lp, float alpha,
+                        double beta_1, double beta_2, float epsilon, float grad_scale, float weight_decay, float lr,
+                        const uint8_t* decay_mask, const void* ctl, vitmi_stream_t stream);
+
 /* SLS data pipeline (models/CvT(Par).py:414-428).
  * vitmi_sls_resize_table (host): cv2 INTER_LINEAR table of one axis, ssize -> dsize:
  *   ofs[d] first source index, w[2d], w[2d+1] its Q11 weights (OpenCV 8-bit fixed point).

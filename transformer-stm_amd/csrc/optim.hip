@@ -102,6 +102,192 @@ __global__ __launch_bounds__(256) void adam_kernel(int64_t n, float* __restrict_
   }
 }
 
+// ---------------------------------------------------------------- global-norm clipping
+// The device record the clipped / skippable step reads (vitmi_clip_finalize writes it).
+struct ClipCtl {
+  float coef;              // what the step multiplies the (scaled) gradients by; exactly 1 = no clipping
+  float norm;              // |grad_scale| * sqrt(sum g^2)
+  uint32_t skip;           // 1: this step leaves p, m, v as they are
+  uint32_t skipped_total;  // running count of skipped steps
+};
+static_assert(sizeof(ClipCtl) == 16, "the clip record is 16 bytes (include/vitmi.h)");
+
+// Sum of squares of one chunk per block, in fp64, in a fixed order (bitwise reproducible, and
+// independent of the grid: a chunk's partial depends on its SUMSQ_CHUNK elements alone):
+//   thread t holds the 16-B groups t, t + 256, ..., t + 256 (U - 1) of the chunk; element e of
+//   its groups goes to accumulator a[e], groups in ascending order; thread sum (a0 + a1) + (a2 + a3);
+//   wave sum: xor butterfly 32, 16, ..., 1 (every lane ends with the same bits); block sum
+//   ((w0 + w1) + w2) + w3 through LDS.
+// (double)g squared is exact (48 significant bits), so only the additions round.  Elements past n
+// count as +0, which leaves every partial's bits unchanged (all terms are >= +0).
+// Measured at the ViT-B arena (85.8 M elements, 343 MB; tools/optim_bench.py): 50-51 us alone, and
+// 58 us more per step with the finalize launch.  Chunk 2048 / 4096 / 8192 / 16384 / 32768 elements:
+// 49 / 50 / 51 / 52 / 52 us (same process, alternating); the finalize block's serial fold grows
+// with the partial count, so 8192.
+constexpr int SUMSQ_THREADS = 256;
+constexpr int SUMSQ_U = VITMI_GRAD_SUMSQ_CHUNK / (SUMSQ_THREADS * 4);
+static_assert(SUMSQ_U >= 1 && SUMSQ_U * SUMSQ_THREADS * 4 == VITMI_GRAD_SUMSQ_CHUNK &&
+                  (VITMI_GRAD_SUMSQ_CHUNK & (VITMI_GRAD_SUMSQ_CHUNK - 1)) == 0,
+              "the chunk is a power of two and a whole number of 16-B groups per thread");
+
+__device__ __forceinline__ double wave_sum_f64(double x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
+
+// block sum of 256 threads' values in the fixed order above; valid in thread 0
+__device__ __forceinline__ double block_sum_f64(double x, double* sh) {
+  x = wave_sum_f64(x);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+__global__ __launch_bounds__(SUMSQ_THREADS) void grad_sumsq_kernel(int64_t n, const float* __restrict__ g,
+                                                                  double* __restrict__ partials) {
+  __shared__ double sh[SUMSQ_THREADS / 64];
+  const int64_t n4 = n / 4;
+  const int64_t base4 = (int64_t)blockIdx.x * (VITMI_GRAD_SUMSQ_CHUNK / 4) + threadIdx.x;
+  f32x4 x[SUMSQ_U];
+#pragma unroll
+  for (int u = 0; u < SUMSQ_U; ++u) {
+    const int64_t i = base4 + (int64_t)u * SUMSQ_THREADS;
+    if (i < n4) {
+      x[u] = ld_s((const f32x4*)g + i);
+    } else {
+      x[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (i == n4) {   // the n % 4 tail sits in the group after the last whole one
+#pragma unroll
+        for (int e = 0; e < 3; ++e)
+          if (i * 4 + e < n) x[u][e] = g[i * 4 + e];
+      }
+    }
+  }
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int u = 0; u < SUMSQ_U; ++u) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const double d = (double)x[u][e];
+      a[e] += d * d;
+    }
+  }
+  const double s = block_sum_f64((a[0] + a[1]) + (a[2] + a[3]), sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// One block: thread t adds partials t, t + 256, ... in ascending order, then the block sum above.
+__global__ __launch_bounds__(SUMSQ_THREADS) void clip_finalize_kernel(int64_t n_partials,
+                                                                     const double* __restrict__ partials,
+                                                                     float grad_scale, float clip_norm,
+                                                                     int skip_nonfinite, ClipCtl* __restrict__ ctl) {
+  __shared__ double sh[SUMSQ_THREADS / 64];
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < n_partials; i += SUMSQ_THREADS) acc += partials[i];
+  const double total = block_sum_f64(acc, sh);
+  if (threadIdx.x != 0) return;
+  const bool finite = isfinite(total);
+  const float norm = (float)(fabs((double)grad_scale) * sqrt(total));
+  float coef = 1.f;
+  if (!finite) coef = __builtin_nanf("");          // nothing hidden: the step's results become NaN
+  else if (clip_norm > 0.f && norm > clip_norm) coef = __fdiv_rn(clip_norm, norm);
+  const uint32_t skip = (skip_nonfinite && !finite) ? 1u : 0u;
+  ctl->coef = coef;
+  ctl->norm = norm;
+  ctl->skip = skip;
+  ctl->skipped_total = ctl->skipped_total + skip;
+}
+
+// adam1 with the clip coefficient and the decoupled weight decay in front (the step of
+// vitmi_adam_step_ctl); with coef == 1 and decay == false it is adam1's ops exactly
+__device__ __forceinline__ void adam1_ctl(const AdamArgs& a, float coef, bool decay, float wd, float lr, float& p,
+                                          float g, float& m, float& v) {
+  if (a.grad_scale != 1.f) g = __fmul_rn(g, a.grad_scale);
+  if (coef != 1.f) g = __fmul_rn(g, coef);
+  if (decay) p = __fsub_rn(p, __fmul_rn(__fmul_rn(p, wd), lr));
+  m = __fadd_rn(m, __fmul_rn(__fsub_rn(g, m), a.one_m_b1));
+  v = __fadd_rn(v, __fmul_rn(__fsub_rn(__fmul_rn(g, g), v), a.one_m_b2));
+  const float den = __fadd_rn(sqrtf(v), a.eps);
+  p = __fsub_rn(p, __fdiv_rn(__fmul_rn(m, a.alpha), den));
+}
+
+// adam_kernel's loop with the record read once per thread.  A skipped step reads p alone and
+// writes only the shadow.  decay_mask: one byte per 64 elements (16 consecutive 16-B groups).
+template <bool LP>
+__global__ __launch_bounds__(256) void adam_ctl_kernel(int64_t n, float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v,
+                                                       bf16* __restrict__ lp, AdamArgs a, float wd, float lr,
+                                                       const uint8_t* __restrict__ mask,
+                                                       const ClipCtl* __restrict__ ctl) {
+  const int64_t n4 = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t t = n4 * 4 + first;   // tail (n % 4) by the first threads
+  const bool tail = t < n && t < n4 * 4 + 4;
+  const float coef = ctl ? ctl->coef : 1.f;
+  if (ctl && ctl->skip) {
+    if constexpr (LP) {
+      for (int64_t i = first; i < n4; i += stride) {
+        const f32x4 pv = ld_s((const f32x4*)p + i);
+        bf16x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = from_f32<bf16>(pv[e]);
+        ((bf16x4*)lp)[i] = o;
+      }
+      if (tail) lp[t] = from_f32<bf16>(p[t]);
+    }
+    return;
+  }
+  constexpr int U = VITMI_ADAM_NT ? 2 : 1;
+  for (int64_t i0 = first; i0 < n4; i0 += U * stride) {
+    f32x4 pv[U], gv[U], mv[U], vv[U];
+    bool dec[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      dec[u] = false;
+      if (u == 0 || i < n4) {
+        pv[u] = ld_s((const f32x4*)p + i);
+        gv[u] = ld_s((const f32x4*)g + i);
+        mv[u] = ld_s((const f32x4*)m + i);
+        vv[u] = ld_s((const f32x4*)v + i);
+        dec[u] = wd != 0.f && (!mask || mask[i >> 4] != 0);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      if (u > 0 && i >= n4) break;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pv[u][e], me = mv[u][e], ve = vv[u][e];
+        adam1_ctl(a, coef, dec[u], wd, lr, pe, gv[u][e], me, ve);
+        pv[u][e] = pe;
+        mv[u][e] = me;
+        vv[u][e] = ve;
+      }
+      st_s((f32x4*)p + i, pv[u]);
+      st_s((f32x4*)m + i, mv[u]);
+      st_s((f32x4*)v + i, vv[u]);
+      if constexpr (LP) {
+        bf16x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = from_f32<bf16>(pv[u][e]);
+        ((bf16x4*)lp)[i] = o;
+      }
+    }
+  }
+  if (tail) {
+    float pe = p[t], me = m[t], ve = v[t];
+    adam1_ctl(a, coef, wd != 0.f && (!mask || mask[t >> 6] != 0), wd, lr, pe, g[t], me, ve);
+    p[t] = pe;
+    m[t] = me;
+    v[t] = ve;
+    if constexpr (LP) lp[t] = from_f32<bf16>(pe);
+  }
+}
+
 }  // namespace vitmi
 
 using namespace vitmi;
@@ -131,5 +317,70 @@ extern "C" int vitmi_adam_step(int64_t n, float* p, const float* g, float* m, fl
   // p, g, m, v read; p, m, v (+ the bf16 shadow) written
   if (p_lp) VITMI_STAT(adam_kernel<true>, 0, (double)n * 30);
   else VITMI_STAT(adam_kernel<false>, 0, (double)n * 28);
+  return VITMI_OK;
+}
+
+extern "C" size_t vitmi_grad_sumsq_partials(int64_t n) {
+  return n <= 0 ? 0 : (size_t)((n + VITMI_GRAD_SUMSQ_CHUNK - 1) / VITMI_GRAD_SUMSQ_CHUNK);
+}
+
+extern "C" int vitmi_grad_sumsq(int64_t n, const float* g, double* partials, vitmi_stream_t stream) {
+  VITMI_CHECK_ARG(n >= 0, "grad_sumsq: n < 0");
+  if (n == 0) return VITMI_OK;
+  VITMI_CHECK_ARG(g && partials, "grad_sumsq: null pointer");
+  VITMI_CHECK_ARG((uintptr_t)g % 16 == 0, "grad_sumsq: the gradient buffer must be 16-byte aligned");
+  VITMI_CHECK_ARG((uintptr_t)partials % 8 == 0, "grad_sumsq: partials must be 8-byte aligned");
+  const size_t chunks = vitmi_grad_sumsq_partials(n);
+  VITMI_CHECK_ARG(chunks <= 0x7fffffffu, "grad_sumsq: n too large for one launch");
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)chunks), dim3(SUMSQ_THREADS), 0, (hipStream_t)stream, n, g,
+                     partials);
+  VITMI_LAUNCH_CHECK("grad_sumsq");
+  // g read once; one double per chunk written
+  VITMI_STAT(grad_sumsq_kernel, 0, (double)n * 4 + (double)chunks * 8);
+  return VITMI_OK;
+}
+
+extern "C" int vitmi_clip_finalize(int64_t n_partials, const double* partials, float grad_scale, float clip_norm,
+                                   int skip_nonfinite, void* ctl, vitmi_stream_t stream) {
+  VITMI_CHECK_ARG(n_partials >= 0, "clip_finalize: n_partials < 0");
+  VITMI_CHECK_ARG(ctl && (partials || n_partials == 0), "clip_finalize: null pointer");
+  VITMI_CHECK_ARG((uintptr_t)partials % 8 == 0, "clip_finalize: partials must be 8-byte aligned");
+  VITMI_CHECK_ARG((uintptr_t)ctl % 16 == 0, "clip_finalize: the clip record must be 16-byte aligned");
+  VITMI_CHECK_ARG(clip_norm >= 0.f, "clip_finalize: clip_norm must be >= 0 (0 = off)");
+  hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(SUMSQ_THREADS), 0, (hipStream_t)stream, n_partials, partials,
+                     grad_scale, clip_norm, skip_nonfinite, (ClipCtl*)ctl);
+  VITMI_LAUNCH_CHECK("clip_finalize");
+  VITMI_STAT(clip_finalize_kernel, 0, (double)n_partials * 8 + 2 * sizeof(ClipCtl));
+  return VITMI_OK;
+}
+
+extern "C" int vitmi_adam_step_ctl(int64_t n, float* p, const float* g, float* m, float* v, void* p_lp, float alpha,
+                                   double beta_1, double beta_2, float epsilon, float grad_scale, float weight_decay,
+                                   float lr, const uint8_t* decay_mask, const void* ctl, vitmi_stream_t stream) {
+  VITMI_CHECK_ARG(n >= 0, "adam_step_ctl: n < 0");
+  if (n == 0) return VITMI_OK;
+  VITMI_CHECK_ARG(p && g && m && v, "adam_step_ctl: null pointer");
+  VITMI_CHECK_ARG(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0,
+                  "adam_step_ctl: fp32 buffers must be 16-byte aligned");
+  VITMI_CHECK_ARG(!p_lp || (uintptr_t)p_lp % 8 == 0, "adam_step_ctl: bf16 shadow must be 8-byte aligned");
+  VITMI_CHECK_ARG((uintptr_t)ctl % 16 == 0, "adam_step_ctl: the clip record must be 16-byte aligned");
+  VITMI_CHECK_ARG(beta_1 >= 0.0 && beta_1 < 1.0 && beta_2 >= 0.0 && beta_2 < 1.0 && epsilon >= 0.f,
+                  "adam_step_ctl: bad hyper-parameters");
+  VITMI_CHECK_ARG(weight_decay >= 0.f, "adam_step_ctl: weight_decay must be >= 0");
+  AdamArgs a{alpha, (float)(1.0 - beta_1), (float)(1.0 - beta_2), epsilon, grad_scale};
+  const int64_t work = (n / 4) > 0 ? (n / 4) : 1;
+  int64_t blocks = (work + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  if (p_lp)
+    hipLaunchKernelGGL(adam_ctl_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v,
+                       (bf16*)p_lp, a, weight_decay, lr, decay_mask, (const ClipCtl*)ctl);
+  else
+    hipLaunchKernelGGL(adam_ctl_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, p, g, m,
+                       v, (bf16*)nullptr, a, weight_decay, lr, decay_mask, (const ClipCtl*)ctl);
+  VITMI_LAUNCH_CHECK("adam_step_ctl");
+  // as adam_step, plus the mask bytes and the record (a skipped step moves less: not known here)
+  const double extra = (decay_mask && weight_decay != 0.f ? (double)((n + 63) / 64) : 0.0) + (ctl ? 16.0 : 0.0);
+  if (p_lp) VITMI_STAT(adam_ctl_kernel<true>, 0, (double)n * 30 + extra);
+  else VITMI_STAT(adam_ctl_kernel<false>, 0, (double)n * 28 + extra);
   return VITMI_OK;
 }

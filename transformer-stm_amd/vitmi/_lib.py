@@ -84,6 +84,10 @@ SIGNATURES = {
     "vitmi_attention_bwd_bias_workspace_size": (S, [I, I, I]),
     "vitmi_attention_bwd_bias": (I, [I, I, I, I, I, F, P, P, P, P, P, P, P, S, P]),
     "vitmi_adam_step": (I, [L, P, P, P, P, P, F, D, D, F, F, P]),
+    "vitmi_grad_sumsq_partials": (S, [L]),
+    "vitmi_grad_sumsq": (I, [L, P, P, P]),
+    "vitmi_clip_finalize": (I, [L, P, F, F, I, P, P]),
+    "vitmi_adam_step_ctl": (I, [L, P, P, P, P, P, F, D, D, F, F, F, F, P, P, P]),
     "vitmi_dense_f32_fwd": (I, [I, I, I, P, L, P, P, P, L, I, P]),
     "vitmi_dense_f32_bwd": (I, [I, I, I, P, L, P, L, P, L, P, P, L, P, P, I, P]),
     "vitmi_avgpool3_fwd": (I, [I, I, I, I, P, L, L, L, P, I, L, L, L, I, P]),

@@ -7,10 +7,15 @@
 ParamArena (every parameter, gradient and moment at the same flat offsets), which also writes
 the bf16 operand shadow the next forward's GEMMs read; models without an arena (the CvT) get
 one launch per parameter tensor.
+
+``global_clipnorm``, ``weight_decay`` and ``skip_nonfinite`` (all off by default) are decided on
+the device: a fixed-order fp64 sum of squares of the gradients (``vitmi_grad_sumsq``), one
+finalize launch that writes a 16-byte record (``vitmi_clip_finalize``), and the step reading it
+(``vitmi_adam_step_ctl``).  No host read, no torch reduction kernel.
 """
 from __future__ import annotations
 
-from typing import Dict, List
+from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -30,17 +35,45 @@ def keras_alpha(lr: float, beta_1: float, beta_2: float, step: int) -> float:
 
 
 class Adam:
-    """keras.optimizers.Adam(learning_rate, beta_1=0.9, beta_2=0.999, epsilon=1e-7).
+    """keras.optimizers.Adam(learning_rate, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
+    global_clipnorm=None, weight_decay=None).
 
     ``target``: a model with ``arena()`` (VisionTransformer: single fused launch + bf16 shadow
     refresh) or an iterable of parameters.  ``grad_scale`` multiplies the gradients as they are
-    read (e.g. 1/world for a sum all-reduce)."""
+    read (e.g. 1/world for a sum all-reduce).
+
+    ``global_clipnorm``: the gradients of the parameters being stepped, times ``grad_scale``, are
+    scaled by ``clipnorm / norm`` when their global L2 norm exceeds it (Keras' ``global_clipnorm``,
+    torch's ``clip_grad_norm_``); the gradient buffers themselves are not modified.  Under data
+    parallelism call ``step()`` after the reducer's ``finish()``: the norm is then over the reduced
+    gradients and every rank decides alike.
+
+    ``weight_decay``: decoupled, ``p -= p * weight_decay * lr`` before the Adam update, as Keras
+    applies it.  It acts on the decay set: by default every parameter with ``ndim >= 2`` except a
+    model's class token and position embedding; ``decay_filter(name, param) -> bool`` overrides
+    that (the name is ``""`` for a plain parameter list).
+
+    ``skip_nonfinite``: a step whose gradient norm is not finite leaves parameters and moments
+    bit for bit as they were.  ``iterations`` still counts it, as Keras' own counter counts
+    ``step()`` calls, and ``alpha`` follows ``iterations``: after a skipped step the bias
+    correction runs slightly ahead of the moments, which errs towards a smaller step and vanishes
+    as ``t`` grows.  ``skipped_steps`` reads the device counter (the only accessor that
+    synchronises); ``last_clip()`` returns the last step's ``(norm, coef)`` as device tensors."""
 
     def __init__(self, target, learning_rate: float = 1e-3, beta_1: float = 0.9, beta_2: float = 0.999,
-                 epsilon: float = 1e-7, grad_scale: float = 1.0):
+                 epsilon: float = 1e-7, grad_scale: float = 1.0, global_clipnorm: Optional[float] = None,
+                 weight_decay: float = 0.0, decay_filter: Optional[Callable[[str, Tensor], bool]] = None,
+                 skip_nonfinite: bool = False):
         self.learning_rate = float(learning_rate)
         self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
         self.grad_scale = float(grad_scale)
+        if global_clipnorm is not None and not float(global_clipnorm) > 0.0:
+            raise ValueError("vitmi Adam: global_clipnorm must be > 0 (None = off)")
+        if not float(weight_decay) >= 0.0:
+            raise ValueError("vitmi Adam: weight_decay must be >= 0")
+        self.global_clipnorm = None if global_clipnorm is None else float(global_clipnorm)
+        self.weight_decay = float(weight_decay)
+        self.skip_nonfinite = bool(skip_nonfinite)
         self.iterations = 0
         self._model = target if hasattr(target, "arena") else None
         if self._model is not None:
@@ -49,11 +82,21 @@ class Adam:
             self.params: List[Tensor] = list(arena.params)
             self._m = torch.zeros_like(arena.flat)
             self._v = torch.zeros_like(arena.flat)
+            names = {id(p): k for k, p in self._model.named_parameters()}
+            no_decay = {id(getattr(self._model, k, None)) for k in ("cls_token", "pos_embed")}
         else:
             self._arena = None
             self.params = [p for p in target if p.requires_grad]
             self._m = [torch.zeros_like(p) for p in self.params]
             self._v = [torch.zeros_like(p) for p in self.params]
+            names, no_decay = {}, set()
+        if decay_filter is not None:
+            self._decays = [bool(decay_filter(names.get(id(p), ""), p)) for p in self.params]
+        else:
+            self._decays = [p.ndim >= 2 and id(p) not in no_decay for p in self.params]
+        self._mask: Optional[Tensor] = None       # arena: one byte per 64 elements, built once
+        self._ctl: Optional[Tensor] = None        # the 16-byte device record (coef, norm, skip, skipped_total)
+        self._partials: Optional[Tensor] = None   # fp64 chunk sums of every stepped run / tensor
         self._ov = None   # overlap_with state
 
     def overlap_with(self, red) -> None:
@@ -67,18 +110,86 @@ class Adam:
         when the backward finishes its first bucket."""
         if self._arena is None:
             raise ValueError("vitmi Adam.overlap_with: needs a model with a parameter arena")
+        if self._use_ctl():
+            raise ValueError("vitmi Adam.overlap_with: global_clipnorm / skip_nonfinite need the whole gradient "
+                             "before the first update; the overlapped per-bucket update cannot use them")
         if red.flat.data_ptr() != self._arena.grad.data_ptr() or red.flat.numel() != self._arena.grad.numel():
             raise ValueError("vitmi Adam.overlap_with: the reducer is not over this model's gradient arena")
         self._ov = {"stream": torch.cuda.Stream(device=self._arena.flat.device), "done": 0, "alpha": None,
-                    "skip": False}
+                    "lr": None, "skip": False}
         red.listeners.append(self._on_bucket)
 
-    def _launch(self, s0: int, e0: int, alpha: float) -> None:
+    # -- clipping / decay / skipping state
+    def _use_ctl(self) -> bool:
+        return self.global_clipnorm is not None or self.skip_nonfinite
+
+    def _ctl_record(self) -> Tensor:
+        if self._ctl is None:
+            dev = self._arena.flat.device if self._arena is not None else self.params[0].device
+            self._ctl = torch.zeros(4, dtype=torch.float32, device=dev)
+            if self._arena is not None:
+                n_part = lib().vitmi_grad_sumsq_partials(self._arena.numel) + len(self.params)
+            else:
+                n_part = sum(lib().vitmi_grad_sumsq_partials(p.numel()) for p in self.params)
+            self._partials = torch.zeros(max(1, n_part), dtype=torch.float64, device=dev)
+        return self._ctl
+
+    def _decay_mask(self) -> Tensor:
+        if self._mask is None:
+            arena = self._arena
+            mask = torch.zeros(arena.numel // arena.ALIGN, dtype=torch.uint8)
+            for p, dec in zip(arena.params, self._decays):
+                if dec:
+                    o = arena.offsets[id(p)] // arena.ALIGN
+                    mask[o:o + (p.numel() + arena.ALIGN - 1) // arena.ALIGN] = 1
+            self._mask = mask.to(arena.flat.device)
+        return self._mask
+
+    def _clip(self, grads: List[Tuple[Tensor, int]]) -> Tensor:
+        """Sum of squares of every (flat gradient, n) into its slice of the partials buffer, then
+        the finalize launch; returns the record the step launches read."""
+        ctl = self._ctl_record()
+        part, k = self._partials, 0
+        for g, n in grads:
+            check(lib().vitmi_grad_sumsq(n, ops._p(g), ops._p(part[k:]), ops._s()), "grad_sumsq")
+            k += lib().vitmi_grad_sumsq_partials(n)
+        check(lib().vitmi_clip_finalize(k, ops._p(part), self.grad_scale, self.global_clipnorm or 0.0,
+                                        int(self.skip_nonfinite), ops._p(ctl), ops._s()), "clip_finalize")
+        return ctl
+
+    @property
+    def skipped_steps(self) -> int:
+        """Steps skipped so far on a non-finite gradient norm (reads the device: synchronises)."""
+        if self._ctl is None:
+            return 0
+        return int(self._ctl.view(torch.int32)[3].item())
+
+    def last_clip(self) -> Tuple[Tensor, Tensor]:
+        """(norm, coef) of the last clipped step: device tensors, views of the record (no sync)."""
+        ctl = self._ctl_record()
+        return ctl[1], ctl[0]
+
+    def _launch(self, s0: int, e0: int, alpha: float, lr: Optional[float] = None,
+                ctl: Optional[Tensor] = None) -> None:
         arena, lp = self._arena, self._arena.flat_lp
-        check(lib().vitmi_adam_step(e0 - s0, ops._p(arena.flat[s0:]), ops._p(arena.grad[s0:]), ops._p(self._m[s0:]),
-                                    ops._p(self._v[s0:]), ops._p(lp[s0:]) if lp is not None else None, alpha,
-                                    self.beta_1, self.beta_2, self.epsilon, self.grad_scale, ops._s()),
-              "adam_step")
+        if ctl is None and self.weight_decay == 0.0:
+            check(lib().vitmi_adam_step(e0 - s0, ops._p(arena.flat[s0:]), ops._p(arena.grad[s0:]),
+                                        ops._p(self._m[s0:]), ops._p(self._v[s0:]),
+                                        ops._p(lp[s0:]) if lp is not None else None, alpha,
+                                        self.beta_1, self.beta_2, self.epsilon, self.grad_scale, ops._s()),
+                  "adam_step")
+            return
+        mask = None
+        if self.weight_decay != 0.0:
+            if s0 % arena.ALIGN:
+                raise RuntimeError("vitmi Adam: weight decay needs step ranges on 64-element boundaries")
+            mask = ops._p(self._decay_mask()[s0 // arena.ALIGN:])
+        check(lib().vitmi_adam_step_ctl(e0 - s0, ops._p(arena.flat[s0:]), ops._p(arena.grad[s0:]),
+                                        ops._p(self._m[s0:]), ops._p(self._v[s0:]),
+                                        ops._p(lp[s0:]) if lp is not None else None, alpha,
+                                        self.beta_1, self.beta_2, self.epsilon, self.grad_scale, self.weight_decay,
+                                        self.learning_rate if lr is None else lr, mask, ops._p(ctl), ops._s()),
+              "adam_step_ctl")
 
     @torch.no_grad()
     def _on_bucket(self, s0: int, e0: int, stream) -> None:
@@ -91,6 +202,7 @@ class Adam:
                 ov["skip"] = True
                 return
             ov["alpha"] = keras_alpha(self.learning_rate, self.beta_1, self.beta_2, self.iterations + 1)
+            ov["lr"] = self.learning_rate
         if s0 != ov["done"]:
             raise RuntimeError("vitmi Adam: gradient buckets finished out of order")
         side = ov["stream"]
@@ -98,7 +210,7 @@ class Adam:
         ready.record(stream if stream is not None else torch.cuda.current_stream(self._arena.flat.device))
         side.wait_event(ready)
         with torch.cuda.stream(side):
-            self._launch(s0, e0, ov["alpha"])
+            self._launch(s0, e0, ov["alpha"], ov["lr"])
         ov["done"] = e0
 
     # -- keras-style schedule hook
@@ -135,34 +247,48 @@ class Adam:
             # Parameters with no gradient (frozen, or zero_grad(set_to_none) and no backward) are
             # not stepped, as in torch / Keras: the launch covers the runs of the arena between them
             stepping = [p.requires_grad and p.grad is not None for p in arena.params]
-            ov, done = self._ov, 0
+            ov, done, lr = self._ov, 0, self.learning_rate
             if ov is not None:
-                done, ov_alpha = ov["done"], ov["alpha"]
-                ov["done"], ov["alpha"], ov["skip"] = 0, None, False
+                if self._use_ctl():
+                    raise ValueError("vitmi Adam: global_clipnorm / skip_nonfinite cannot be used with overlap_with")
+                done, ov_alpha, ov_lr = ov["done"], ov["alpha"], ov["lr"]
+                ov["done"], ov["alpha"], ov["lr"], ov["skip"] = 0, None, None, False
                 if done:
                     # the buckets the backward finished were stepped on the side stream
                     torch.cuda.current_stream(arena.flat.device).wait_stream(ov["stream"])
-                    alpha = ov_alpha
+                    alpha, lr = ov_alpha, ov_lr
             if not any(stepping):
                 return
             lp = arena.flat_lp
             if not all(stepping):
                 arena.refresh_lp()          # the skipped parameters' shadow must be current too
             arena.bind_grads(fill_missing=all(stepping))
-            for s0, e0 in arena.runs(stepping):
-                s0 = max(s0, done)
-                if e0 > s0:
-                    self._launch(s0, e0, alpha)
+            runs = [(max(s0, done), e0) for s0, e0 in arena.runs(stepping) if e0 > max(s0, done)]
+            # the norm is over the gradients of the parameters being stepped, and only those
+            ctl = self._clip([(arena.grad[s0:], e0 - s0) for s0, e0 in runs]) if self._use_ctl() else None
+            for s0, e0 in runs:
+                self._launch(s0, e0, alpha, lr, ctl)
             arena.mark_lp_fresh()
             return
-        for p, m, v in zip(self.params, self._m, self._v):
-            if p.grad is None:
-                continue
+        todo = [(p, m, v, dec) for p, m, v, dec in zip(self.params, self._m, self._v, self._decays)
+                if p.grad is not None]
+        for p, _, _, _ in todo:
             if not (p.is_contiguous() and p.grad.is_contiguous()):
                 raise RuntimeError("vitmi Adam: parameters and gradients must be contiguous")
-            check(lib().vitmi_adam_step(p.numel(), ops._p(p), ops._p(p.grad), ops._p(m), ops._p(v), None, alpha,
-                                        self.beta_1, self.beta_2, self.epsilon, self.grad_scale, ops._s()),
-                  "adam_step")
+        if not todo:
+            return
+        ctl = self._clip([(p.grad, p.numel()) for p, _, _, _ in todo]) if self._use_ctl() else None
+        for p, m, v, dec in todo:
+            if ctl is None and self.weight_decay == 0.0:
+                check(lib().vitmi_adam_step(p.numel(), ops._p(p), ops._p(p.grad), ops._p(m), ops._p(v), None, alpha,
+                                            self.beta_1, self.beta_2, self.epsilon, self.grad_scale, ops._s()),
+                      "adam_step")
+            else:
+                # a decaying tensor decays whole (NULL mask); one that does not gets weight_decay 0
+                check(lib().vitmi_adam_step_ctl(p.numel(), ops._p(p), ops._p(p.grad), ops._p(m), ops._p(v), None,
+                                                alpha, self.beta_1, self.beta_2, self.epsilon, self.grad_scale,
+                                                self.weight_decay if dec else 0.0, self.learning_rate, None,
+                                                ops._p(ctl), ops._s()), "adam_step_ctl")
             # the kernel wrote through a raw pointer: bump the version counter, so a ParamArena
             # that owns p (its bf16 operand shadow is keyed on these counters) re-casts it
             torch.autograd.graph.increment_version(p)
