@@ -434,6 +434,59 @@ int vitmi_adam_step_ctl(int64_t n, float* p, const float* g, float* m, float* v,
                         double beta_1, double beta_2, float epsilon, float grad_scale, float weight_decay, float lr,
                         const uint8_t* decay_mask, const void* ctl, vitmi_stream_t stream);
 
+/* The classification recipe on the device (csrc/loss.hip): softmax cross-entropy on label, mixed-pair
+ * and dense soft targets with label smoothing and top-1 / top-k scoring, and the mixup / cutmix image
+ * pass (timm Mixup + SoftTargetCrossEntropy; tf.keras CategoricalCrossentropy(label_smoothing=)).
+ *
+ * vitmi_softmax_xent: logits fp32 [B][ldl], C classes.  The target distribution of row b is
+ *   label form (soft == NULL):  t = lam[b] onehot(label_a[b]) + (1 - lam[b]) onehot(label_b[b]);
+ *     label_b and lam are both NULL (t = onehot(label_a[b])) or both given;
+ *   dense form (soft fp32 [B][lds]):  t = soft[b][:], which need not sum to 1;
+ *   q = (1 - smoothing) t + smoothing sum(t) / C    (smoothing == 0: q = t exactly).
+ *   row_loss[b]   = lse_b sum(q) - sum_c q_c z_c    (a class with q_c == 0 adds nothing, even at
+ *                   z_c = -inf: masked classes give a finite loss and a zero gradient there)
+ *   dlogits[b][c] = (softmax(z)_c sum(q) - q_c) / B,  softmax as exp(z - max) / sum;  [B][lddl],
+ *                   columns past C are not written
+ *   loss[0]       = (float)(sum_b (double)row_loss[b] / B)
+ *   Label values are not read on the host.  A label outside [0, C) matches no class: it keeps its
+ *   weight in sum(t) but has no indexed logit and no gradient entry (row_loss = lse sum(q) minus the
+ *   smoothing term alone), and the row is a miss.
+ *   One wave64 per row, one online (max, sum) pass with 16-byte loads when C % 4 == 0, ldl (lds, lddl)
+ *   % 4 == 0 and the bases are 16-byte aligned, scalar loads otherwise; the gradient leaves from
+ *   registers for C <= 1024 and from a second (L2) pass above.  A row's results depend on that row
+ *   alone; a second launch of one block folds the rows in fp64 (thread t takes rows t, t + 256, ... in
+ *   ascending order, then a fixed tree, as vitmi_clip_finalize): results are bitwise reproducible.
+ *   row_loss, loss and dlogits may each be NULL, but not all three without metrics.
+ * metrics (optional): a 32-byte, 16-byte aligned device record the caller zeroes once,
+ *     struct { double loss_sum; uint64_t rows; uint64_t top1; uint64_t topk; }
+ *   The fold launch ADDS this batch: loss_sum += sum_b row_loss[b], rows += B, and the hit counts; the
+ *   host reads it once per epoch.  Hits are scored against y = label_a[b] (required with metrics, in the
+ *   dense form too), on the fp32 logits exactly: row b is a top-k hit iff
+ *     #{c : z_c > z_y or (z_c == z_y and c < y)} < k        (ties go to the lower class index)
+ *   top-1 is the same rule with k = 1; a row whose z_y is NaN, or whose label is outside [0, C), is a
+ *   miss.  topk in 0..C, >= 1 with metrics.
+ * workspace: vitmi_softmax_xent_workspace_size(B) bytes (row losses when row_loss is NULL, one flag
+ *   byte per row); required with metrics, or with loss when row_loss is NULL; 4-byte aligned.
+ *   B > 0, 1 <= C <= 65535, ldl / lds / lddl >= C, 0 <= smoothing < 1.
+ *
+ * vitmi_mix_batch: mixup and cutmix of an fp32 [B][C][H][W] batch in one pass,
+ *   out[b,c,y,x] = (y0 <= y < y1 && x0 <= x < x1) ? img[perm[b],c,y,x]
+ *                                                 : lam[b] img[b,c,y,x] + (1 - lam[b]) img[perm[b],c,y,x]
+ *   with the per-sample device tables perm int32 [B], lam fp32 [B], box int32 [B][4] = (y0, y1, x0, x1).
+ *   An empty box gives pure mixup, lam = 1 with a box pure cutmix.  1 - lam is formed once in fp32, the
+ *   two products are rounded separately and then added (no FMA): bit-identical to a float32 evaluation.
+ *   A sample with lam == 1 and an empty box is a copy whose partner is not read (a NaN there cannot leak
+ *   through 0 * NaN).  Box edges are clamped to the image and perm[b] outside [0, B) is taken as b, in
+ *   the kernel.  16-byte accesses along x when W % 4 == 0 and img, out are 16-byte aligned (selected per
+ *   element inside a group that straddles a box edge), scalar otherwise.  out must not overlap img. */
+size_t vitmi_softmax_xent_workspace_size(int B);
+int vitmi_softmax_xent(int B, int C, const float* logits, int64_t ldl, const int64_t* label_a, const int64_t* label_b,
+                       const float* lam, const float* soft, int64_t lds, float smoothing, int topk, float* row_loss,
+                       float* loss, float* dlogits, int64_t lddl, void* metrics, void* workspace,
+                       size_t workspace_bytes, vitmi_stream_t stream);
+int vitmi_mix_batch(int B, int C, int H, int W, const float* img, const int* perm, const float* lam, const int* box,
+                    float* out, vitmi_stream_t stream);
+
 /* SLS data pipeline (models/CvT(Par).py:414-428).
  * vitmi_sls_resize_table (host): cv2 INTER_LINEAR table of one axis, ssize -> dsize:
  *   ofs[d] first source index, w[2d], w[2d+1] its Q11 weights (OpenCV 8-bit fixed point).

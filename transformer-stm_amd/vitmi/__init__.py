@@ -11,3 +11,12 @@ __version__ = "0.1.0"
 def _lazy():
     from . import modules, ops  # noqa: F401
     return modules, ops
+
+
+def __getattr__(name):
+    # vitmi.losses / vitmi.augment (the classification recipe), imported on first use like the rest:
+    # importing the package alone stays free of torch
+    if name in ("losses", "augment"):
+        import importlib
+        return importlib.import_module("." + name, __name__)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

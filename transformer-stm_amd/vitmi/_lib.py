@@ -88,6 +88,9 @@ SIGNATURES = {
     "vitmi_grad_sumsq": (I, [L, P, P, P]),
     "vitmi_clip_finalize": (I, [L, P, F, F, I, P, P]),
     "vitmi_adam_step_ctl": (I, [L, P, P, P, P, P, F, D, D, F, F, F, F, P, P, P]),
+    "vitmi_softmax_xent_workspace_size": (S, [I]),
+    "vitmi_softmax_xent": (I, [I, I, P, L, P, P, P, P, L, F, I, P, P, P, L, P, P, S, P]),
+    "vitmi_mix_batch": (I, [I, I, I, I, P, P, P, P, P, P]),
     "vitmi_dense_f32_fwd": (I, [I, I, I, P, L, P, P, P, L, I, P]),
     "vitmi_dense_f32_bwd": (I, [I, I, I, P, L, P, L, P, L, P, P, L, P, P, I, P]),
     "vitmi_avgpool3_fwd": (I, [I, I, I, I, P, L, L, L, P, I, L, L, L, I, P]),

@@ -568,6 +568,60 @@ def loss_fwd_bwd(logits: Tensor, target: Tensor, kind: int):
     return loss, dl
 
 
+def softmax_xent(logits: Tensor, label_a: Optional[Tensor] = None, label_b: Optional[Tensor] = None,
+                 lam: Optional[Tensor] = None, soft: Optional[Tensor] = None, smoothing: float = 0.0, topk: int = 0,
+                 metrics: Optional[Tensor] = None, want_row_loss: bool = True, want_loss: bool = True,
+                 want_grad: bool = True, dlogits: Optional[Tensor] = None):
+    """Softmax cross-entropy forward + backward and top-1 / top-k scoring in one launch pair
+    (vitmi_softmax_xent).  logits fp32 [B, C] (rows may be strided); label_a / label_b int64 [B], lam
+    fp32 [B] (the mixed pair), or soft fp32 [B, C] (dense target); metrics: the 32-byte device record
+    (float64 [4] storage) the batch is added to.  ``dlogits``: an output [B, C] (rows may be strided)
+    to write instead of a fresh one.  Returns (row_loss [B] | None, loss [] | None, dlogits | None)."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2
+    B, C = logits.shape
+    _, ldl = _rows(logits)
+    dev = logits.device
+
+    def lab(t):
+        return None if t is None else t.to(device=dev, dtype=torch.int64).contiguous()
+
+    label_a, label_b = lab(label_a), lab(label_b)
+    lam = None if lam is None else lam.to(device=dev, dtype=torch.float32).contiguous()
+    lds = 0
+    if soft is not None:
+        soft = soft.to(device=dev, dtype=torch.float32)
+        assert soft.shape == logits.shape
+        _, lds = _rows(soft)
+    row = torch.empty(B, dtype=torch.float32, device=dev) if want_row_loss else None
+    loss = torch.empty((), dtype=torch.float32, device=dev) if want_loss else None
+    if dlogits is None and want_grad:
+        dlogits = torch.empty(B, C, dtype=torch.float32, device=dev)
+    lddl = 0
+    if dlogits is not None:
+        assert dlogits.dtype == torch.float32 and dlogits.shape == logits.shape
+        _, lddl = _rows(dlogits)
+    ws = _ws(lib().vitmi_softmax_xent_workspace_size(B), logits)
+    check(lib().vitmi_softmax_xent(B, C, _p(logits), ldl, _p(label_a), _p(label_b), _p(lam), _p(soft), lds,
+                                   float(smoothing), int(topk), _p(row), _p(loss), _p(dlogits), lddl, _p(metrics),
+                                   _p(ws), ws.numel(), _s()), "softmax_xent")
+    return row, loss, dlogits
+
+
+def mix_batch(img: Tensor, perm: Tensor, lam: Tensor, box: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """Mixup / cutmix of an fp32 [B, C, H, W] batch in one pass (vitmi_mix_batch): perm int32 [B],
+    lam fp32 [B], box int32 [B, 4] = (y0, y1, x0, x1), all on the device."""
+    assert img.dtype == torch.float32 and img.dim() == 4 and img.is_contiguous()
+    B, C, H, W = img.shape
+    assert perm.dtype == torch.int32 and perm.shape == (B,) and perm.is_contiguous()
+    assert lam.dtype == torch.float32 and lam.shape == (B,) and lam.is_contiguous()
+    assert box.dtype == torch.int32 and box.shape == (B, 4) and box.is_contiguous()
+    if out is None:
+        out = torch.empty_like(img)
+    assert out.dtype == torch.float32 and out.shape == img.shape and out.is_contiguous()
+    check(lib().vitmi_mix_batch(B, C, H, W, _p(img), _p(perm), _p(lam), _p(box), _p(out), _s()), "mix_batch")
+    return out
+
+
 def cast_bf16(src: Tensor, dst: Optional[Tensor] = None) -> Tensor:
     assert src.dtype == torch.float32 and src.is_contiguous()
     if dst is None:
