@@ -322,6 +322,36 @@ int vitmi_dropout_apply(int64_t M, int64_t N, const float* x, int64_t ldx, void*
                         vitmi_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Stochastic depth / drop path (old_codes/MS_CvT.py Block.forward: x + drop_path(branch)).
+ * One keep decision per SAMPLE of a drop-path site: sample b is kept iff
+ * vitmi_dropout_hash(seed, path_site, b, 0) >= path_thresh (thresh = round(p * 2^32) as for
+ * dropout); its factor is path_scale = 1/(1-p) if kept, else 0.  Row r of an [M, .] operand
+ * belongs to sample r / rows_per_sample (the sequence length, cls token included).  Like the
+ * dropout mask the factor is a pure function of its coordinates and is never stored.
+ * Both calls need rows_per_sample >= 1, M % rows_per_sample == 0 and M * rows_per_sample <=
+ * 2^32 (where the kernels' multiply-high row -> sample mapping is exact).  drop_thresh == 0
+ * means "no element dropout" (drop_site / drop_scale are then ignored).
+ *
+ * vitmi_linear_fwd with the RESIDUAL epilogue (the only one accepted; dtype F32 or BF16) and
+ * the sample factor fused in:
+ *   y = residual + (acc + bias) * [element keep * drop_scale] * f[row / rows_per_sample]
+ * (the element dropout of vitmi_linear_fwd_dropout first, then the sample factor). */
+int vitmi_linear_fwd_droppath(int dtype, int64_t M, int64_t N, int64_t K, const void* x,
+                              const void* w, const float* bias, void* y, int y_dtype, int epilogue,
+                              const float* residual, void* workspace, size_t ws_bytes,
+                              uint32_t seed, uint32_t drop_site, uint32_t drop_thresh,
+                              float drop_scale, int64_t rows_per_sample, uint32_t path_site,
+                              uint32_t path_thresh, float path_scale, vitmi_stream_t stream);
+/* y[M][ldy] (f32 or bf16) = x[M][ldx] (f32) * f[row / rows_per_sample], with drop_thresh != 0
+ * also times the element-dropout mask (keep * drop_scale) of drop_site, in the same pass: the
+ * gradient entering a dropped branch in the backward.  Rows of dropped samples are zeros.
+ * N % 4 == 0; alignment and leading-dimension rules of vitmi_dropout_apply. */
+int vitmi_droppath_apply(int64_t M, int64_t N, const float* x, int64_t ldx, void* y, int y_dtype,
+                         int64_t ldy, int64_t rows_per_sample, uint32_t seed, uint32_t path_site,
+                         uint32_t path_thresh, float path_scale, uint32_t drop_site,
+                         uint32_t drop_thresh, float drop_scale, vitmi_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * CvT stages (the reference's actual SLS model, models/CvT(Par).py:66-72).
  *
  * ConvEmbed = layers.Conv2D(D, kernel=k, strides=s, padding='same') (:203-212) as a GEMM over

@@ -123,6 +123,22 @@ __host__ __device__ inline uint32_t drop_hash(uint32_t row_key, uint32_t col) {
   return fmix32(row_key ^ (col * 0x85EBCA77u));
 }
 
+// ---------------------------------------------------------------- drop path (stochastic depth)
+// One keep decision per sample of a drop-path site: sample b is kept iff drop_hash(drop_row_key(seed,
+// site, b), 0) >= thresh (the dropout hash at row = sample, col = 0; include/vitmi.h).  Row r of an
+// [M, .] operand belongs to sample r / S.  The kernels divide by a multiply: with magic =
+// floor(2^32 / S) + 1 = (2^32 + e) / S, 1 <= e <= S, mulhi(r, magic) = floor(r / S + r e / (S 2^32)),
+// which is floor(r / S) whenever r e < 2^32; r < M and e <= S, so M * S <= 2^32 is enough
+// (path_map_exact, the entry points' host check).  S = 1 has no 32-bit magic and maps r to itself.
+__host__ __device__ inline bool path_keep(uint32_t seed, uint32_t site, uint32_t sample, uint32_t thresh) {
+  return drop_hash(drop_row_key(seed, site, sample), 0u) >= thresh;
+}
+inline uint32_t path_magic(uint32_t S) { return S < 2 ? 0u : (uint32_t)((1ull << 32) / S) + 1u; }
+inline bool path_map_exact(int64_t M, int64_t S) { return M <= 0 || (S >= 1 && S <= (1ll << 32) / M); }
+__device__ __forceinline__ uint32_t path_sample(uint32_t row, uint32_t S, uint32_t magic) {
+  return S == 1 ? row : __umulhi(row, magic);
+}
+
 // ---------------------------------------------------------------- reductions
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

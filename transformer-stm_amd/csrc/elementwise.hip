@@ -432,6 +432,40 @@ __global__ void dropout_apply_kernel(int64_t M, int64_t N, const float* __restri
   }
 }
 
+// y[r][c] = x[r][c] * f[r / S], f = the drop-path factor of the row's sample (common.h path_keep);
+// DROP: times the element-dropout mask of (dsite, dthresh, dscale) as well, in the same pass.  Rows
+// of dropped samples are written as zeros without reading x.  4 columns per thread; N % 4 == 0.
+template <typename TO, bool DROP>
+__global__ void droppath_apply_kernel(int64_t M, int64_t N, const float* __restrict__ x, int64_t ldx,
+                                      TO* __restrict__ y, int64_t ldy, uint32_t S, uint32_t magic, uint32_t seed,
+                                      uint32_t psite, uint32_t pthresh, float pscale, uint32_t dsite,
+                                      uint32_t dthresh, float dscale) {
+  const int64_t n4 = N / 4, total = M * n4;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / n4, c = (i - r * n4) * 4;
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    if (path_keep(seed, psite, path_sample((uint32_t)r, S, magic), pthresh)) {
+      const f32x4 v = *(const f32x4*)(x + r * ldx + c);
+      if constexpr (DROP) {
+        const uint32_t rk = drop_row_key(seed, dsite, (uint32_t)r);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = drop_hash(rk, (uint32_t)(c + e)) >= dthresh ? v[e] * dscale * pscale : 0.f;
+      } else {
+        o = v * pscale;
+      }
+    }
+    if constexpr (sizeof(TO) == 4) {
+      *(f32x4*)(y + r * ldy + c) = o;
+    } else {
+      bf16x4 b;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) b[e] = (bf16)o[e];
+      *(bf16x4*)(y + r * ldy + c) = b;
+    }
+  }
+}
+
 static unsigned grid_for(int64_t work, int per_block = 256) {
   int64_t g = (work + per_block - 1) / per_block;
   if (g > 8192) g = 8192;
@@ -601,6 +635,46 @@ extern "C" int vitmi_dropout_apply(int64_t M, int64_t N, const float* x, int64_t
     hipLaunchKernelGGL(dropout_apply_kernel<bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, M, N, x, ldx,
                        (bf16*)y, ldy, seed, site, thresh, scale);
   VITMI_LAUNCH_CHECK("dropout_apply");
+  return VITMI_OK;
+}
+
+extern "C" int vitmi_droppath_apply(int64_t M, int64_t N, const float* x, int64_t ldx, void* y, int y_dtype,
+                                    int64_t ldy, int64_t rows_per_sample, uint32_t seed, uint32_t path_site,
+                                    uint32_t path_thresh, float path_scale, uint32_t drop_site,
+                                    uint32_t drop_thresh, float drop_scale, vitmi_stream_t stream) {
+  VITMI_CHECK_ARG(x && y, "droppath_apply: null pointer");
+  VITMI_CHECK_ARG(y_dtype == VITMI_F32 || y_dtype == VITMI_BF16, "droppath_apply: bad dtype %d", y_dtype);
+  VITMI_CHECK_ARG(M >= 0 && N >= 0, "droppath_apply: negative size");
+  VITMI_CHECK_ARG(N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= N && ldy >= N,
+                  "droppath_apply: N and leading dims must be multiples of 4");
+  VITMI_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 8) == 0, "droppath_apply: alignment");
+  VITMI_CHECK_ARG(rows_per_sample >= 1, "droppath_apply: rows_per_sample must be >= 1 (got %lld)",
+                  (long long)rows_per_sample);
+  VITMI_CHECK_ARG(M % rows_per_sample == 0, "droppath_apply: M = %lld is not a multiple of rows_per_sample = %lld",
+                  (long long)M, (long long)rows_per_sample);
+  VITMI_CHECK_ARG(path_map_exact(M, rows_per_sample), "droppath_apply: M * rows_per_sample must be <= 2^32 "
+                  "(the row -> sample mapping is exact only there)");
+  if (M == 0 || N == 0) return VITMI_OK;
+  const unsigned grid = grid_for(M * N / 4);
+  const uint32_t S = (uint32_t)rows_per_sample, magic = path_magic(S);
+  const hipStream_t s = (hipStream_t)stream;
+  // drop_thresh 0 keeps every element: the sample factor alone
+#define VITMI_DP_LAUNCH(TO, DROP)                                                                            \
+  do {                                                                                                       \
+    hipLaunchKernelGGL((droppath_apply_kernel<TO, DROP>), dim3(grid), dim3(256), 0, s, M, N, x, ldx, (TO*)y, \
+                       ldy, S, magic, seed, path_site, path_thresh, path_scale, drop_site, drop_thresh,      \
+                       drop_scale);                                                                          \
+    VITMI_STAT((droppath_apply_kernel<TO, DROP>), 0, (double)M * N * (4 + sizeof(TO)));                      \
+  } while (0)
+  if (y_dtype == VITMI_F32) {
+    if (drop_thresh) VITMI_DP_LAUNCH(float, true);
+    else VITMI_DP_LAUNCH(float, false);
+  } else {
+    if (drop_thresh) VITMI_DP_LAUNCH(bf16, true);
+    else VITMI_DP_LAUNCH(bf16, false);
+  }
+#undef VITMI_DP_LAUNCH
+  VITMI_LAUNCH_CHECK("droppath_apply");
   return VITMI_OK;
 }
 

@@ -111,6 +111,11 @@ struct GemmArgs {
     int tiles_n, tile0;
   } grp[4];
   int ngrp;
+  // stochastic depth of the *_PATH residual epilogues: row r belongs to sample r / path_S, and the
+  // whole sample is kept iff drop_hash(drop_row_key(drop_seed, path_site, sample), 0) >= path_thresh
+  // (factor path_scale, else 0).  path_magic: path_sample() in common.h
+  uint32_t path_site, path_thresh, path_S, path_magic;
+  float path_scale;
 };
 constexpr int GRP_MAX = 4;
 
@@ -158,21 +163,31 @@ __device__ __forceinline__ void tile_rc(const GemmArgs& g, int tl, int& tm, int&
 // internal epilogues: split-K partial slab, and GELU / residual with a fused dropout
 // EPI_GELU_X3: BIAS_GELU with the activation written split, [hi | hi | lo] (VITMI_EPI_SPLIT_X3)
 // EPI_GELU_F8: BIAS_GELU with the activation written as VITMI_BF16F8 A-operand rows (VITMI_EPI_SPLIT_F8)
-enum { EPI_PARTIAL = 100, EPI_GELU_DROP = 101, EPI_RESIDUAL_DROP = 102, EPI_GELU_X3 = 103, EPI_GELU_F8 = 104 };
-// the public epilogue an internal one extends, and whether it drops
+// EPI_RESIDUAL_PATH: RESIDUAL with the branch scaled by its sample's drop-path factor;
+// EPI_RESIDUAL_DROP_PATH: the element dropout of RESIDUAL_DROP first, then the sample factor
+enum { EPI_PARTIAL = 100, EPI_GELU_DROP = 101, EPI_RESIDUAL_DROP = 102, EPI_GELU_X3 = 103, EPI_GELU_F8 = 104,
+       EPI_RESIDUAL_PATH = 105, EPI_RESIDUAL_DROP_PATH = 106 };
+// the public epilogue an internal one extends, whether it drops elements and whether it drops paths
 template <int EPI> struct EpiOf {
+  static constexpr bool path = EPI == EPI_RESIDUAL_PATH || EPI == EPI_RESIDUAL_DROP_PATH;
   static constexpr int base = EPI == EPI_GELU_DROP || EPI == EPI_GELU_X3 || EPI == EPI_GELU_F8 ? VITMI_EPI_BIAS_GELU
-                              : EPI == EPI_RESIDUAL_DROP ? VITMI_EPI_RESIDUAL : EPI;
-  static constexpr bool drop = EPI == EPI_GELU_DROP || EPI == EPI_RESIDUAL_DROP;
+                              : EPI == EPI_RESIDUAL_DROP || path ? VITMI_EPI_RESIDUAL : EPI;
+  static constexpr bool drop = EPI == EPI_GELU_DROP || EPI == EPI_RESIDUAL_DROP || EPI == EPI_RESIDUAL_DROP_PATH;
 };
 static inline int epi_base(int epi) {
   return epi == EPI_GELU_DROP || epi == EPI_GELU_X3 || epi == EPI_GELU_F8 ? VITMI_EPI_BIAS_GELU
-         : epi == EPI_RESIDUAL_DROP ? VITMI_EPI_RESIDUAL : epi;
+         : epi == EPI_RESIDUAL_DROP || epi == EPI_RESIDUAL_PATH || epi == EPI_RESIDUAL_DROP_PATH ? VITMI_EPI_RESIDUAL
+         : epi;
 }
 // dropout factor (0 or 1/(1-p)) of output element (row, col)
 __device__ __forceinline__ float drop_factor(const GemmArgs& g, int64_t row, int64_t col) {
   return drop_hash(drop_row_key(g.drop_seed, g.drop_site, (uint32_t)row), (uint32_t)col) >= g.drop_thresh
              ? g.drop_scale : 0.f;
+}
+// drop-path factor (0 or 1/(1-p)) of the sample that owns output row `row`
+__device__ __forceinline__ float path_factor(const GemmArgs& g, int64_t row) {
+  return path_keep(g.drop_seed, g.path_site, path_sample((uint32_t)row, g.path_S, g.path_magic), g.path_thresh)
+             ? g.path_scale : 0.f;
 }
 
 __device__ __forceinline__ int swz_k(int row) { return (row >> 1) & 7; }
@@ -329,6 +344,11 @@ __device__ __forceinline__ void epi_store(const GemmArgs& g, int64_t row, int64_
     ((TC*)g.C)[row * g.ldc + col] = from_f32<TC>(gelu_f(u) * f);
   } else if constexpr (EPI == EPI_RESIDUAL_DROP) {
     ((float*)g.C)[row * g.ldc + col] = g.residual[row * g.ldr + col] + (acc + biasv) * drop_factor(g, row, col);
+  } else if constexpr (EPI == EPI_RESIDUAL_PATH) {
+    ((float*)g.C)[row * g.ldc + col] = g.residual[row * g.ldr + col] + (acc + biasv) * path_factor(g, row);
+  } else if constexpr (EPI == EPI_RESIDUAL_DROP_PATH) {
+    ((float*)g.C)[row * g.ldc + col] =
+        g.residual[row * g.ldr + col] + (acc + biasv) * drop_factor(g, row, col) * path_factor(g, row);
   } else if constexpr (EPI == EPI_PARTIAL) {
     ((float*)g.C)[blockIdx.z * g.split_stride + row * g.ldc + col] = acc;
   } else if constexpr (EPI == VITMI_EPI_STORE) {
@@ -641,6 +661,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
   __shared__ __attribute__((aligned(16))) char smem[2 * STAGE + 2048 + NWAVES * EPI_SCR];
   constexpr int EB = EpiOf<EPI>::base;         // public epilogue (the *_DROP ones extend one)
   constexpr bool DROP = EpiOf<EPI>::drop;
+  constexpr bool PATH = EpiOf<EPI>::path;      // (the *_PATH ones: a factor per sample of path_S rows)
   constexpr bool HAS_BIAS = EB == VITMI_EPI_STORE || EB == VITMI_EPI_BIAS_GELU || EB == VITMI_EPI_RESIDUAL;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1253,6 +1274,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
 #pragma unroll
             for (int h = 0; h < RB; ++h) {
               const int mi = RB * mp + h;
+              [[maybe_unused]] float pf = 1.f;   // the lane's row of this row group: its sample's factor
+              if constexpr (PATH) pf = path_factor(g, m0 + wm * 128 + mi * 16 + lr);
 #pragma unroll
               for (int pp = 0; pp < 2; ++pp) {
 #pragma unroll
@@ -1269,6 +1292,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
                     for (int e = 0; e < 4; ++e)
                       v[e] *= drop_hash(rk, (uint32_t)(colc[ni] + e)) >= g.drop_thresh ? g.drop_scale : 0.f;
                   }
+                  if constexpr (PATH) v *= pf;
                   *pr = v + *pr;
                 }
                 lane_xchg();
@@ -1526,6 +1550,17 @@ __global__ __launch_bounds__(256) void gemm_tail_fixup_kernel(GemmArgs g, int nt
       *(f32x4*)((float*)g.C + row * g.ldc + col) = (r + a) + bv;
       continue;
     }
+    if constexpr (EpiOf<EPI>::path) {
+      // the same vectors with the branch scaled: residual + (acc + bias) [* element keep] * sample factor
+      const f32x4 r = *(const f32x4*)(g.residual + row * g.ldr + col);
+      f32x4 v = a + (g.bias ? *(const f32x4*)(g.bias + col) : f32x4{0.f, 0.f, 0.f, 0.f});
+      if constexpr (EpiOf<EPI>::drop) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] *= drop_factor(g, row, col + j);
+      }
+      *(f32x4*)((float*)g.C + row * g.ldc + col) = v * path_factor(g, row) + r;
+      continue;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (col + j >= g.N) break;
@@ -1766,6 +1801,12 @@ static int dispatch(int ak, int bk, int c_dtype, int epi, GemmArgs g, int splits
     case EPI_RESIDUAL_DROP:
       if (!(ak && bk)) break;
       return launch_t<T, true, true, EPI_RESIDUAL_DROP, float>(g, splits, big, s);
+    case EPI_RESIDUAL_PATH:
+      if (!(ak && bk)) break;
+      return launch_t<T, true, true, EPI_RESIDUAL_PATH, float>(g, splits, big, s);
+    case EPI_RESIDUAL_DROP_PATH:
+      if (!(ak && bk)) break;
+      return launch_t<T, true, true, EPI_RESIDUAL_DROP_PATH, float>(g, splits, big, s);
     case EPI_GELU_X3:   // forward linear layers, bf16 operands and output only (gemm_impl checks)
       if (!(ak && bk)) break;
       if constexpr (std::is_same<T, bf16>::value) return launch_t<T, true, true, EPI_GELU_X3, bf16>(g, splits, big, s);
@@ -1897,6 +1938,8 @@ static int gemm_impl(int dtype, int ak, int bk, int64_t M, int64_t N, int64_t K,
   if (drop) {
     g.drop_seed = drop->drop_seed; g.drop_site = drop->drop_site;
     g.drop_thresh = drop->drop_thresh; g.drop_scale = drop->drop_scale;
+    g.path_site = drop->path_site; g.path_thresh = drop->path_thresh; g.path_scale = drop->path_scale;
+    g.path_S = drop->path_S; g.path_magic = drop->path_magic;
   }
   int splits = 1;
   if (allow_split && epi == VITMI_EPI_ACCUM) splits = choose_splits(dtype, M, N, K, g_reserved.load(std::memory_order_relaxed));
@@ -2187,6 +2230,33 @@ extern "C" int vitmi_linear_fwd_dropout(int dtype, int64_t M, int64_t N, int64_t
   d.drop_seed = seed; d.drop_site = site; d.drop_thresh = thresh; d.drop_scale = scale;
   const int epi = (eb == VITMI_EPI_BIAS_GELU ? EPI_GELU_DROP : EPI_RESIDUAL_DROP) | (epilogue & VITMI_EPI_AUX_TILED);
   return gemm_impl(dtype, 1, 1, M, N, K, x, K, w, K, y, N, y_dtype, epi, bias, aux, N, residual, N,
+                   workspace, ws_bytes, (hipStream_t)stream, false, &d);
+}
+
+extern "C" int vitmi_linear_fwd_droppath(int dtype, int64_t M, int64_t N, int64_t K, const void* x,
+                                         const void* w, const float* bias, void* y, int y_dtype,
+                                         int epilogue, const float* residual, void* workspace,
+                                         size_t ws_bytes, uint32_t seed, uint32_t drop_site,
+                                         uint32_t drop_thresh, float drop_scale, int64_t rows_per_sample,
+                                         uint32_t path_site, uint32_t path_thresh, float path_scale,
+                                         vitmi_stream_t stream) {
+  VITMI_CHECK_ARG(epilogue == VITMI_EPI_RESIDUAL, "linear_fwd_droppath: epilogue must be RESIDUAL (got %d)", epilogue);
+  VITMI_CHECK_ARG(dtype == VITMI_F32 || dtype == VITMI_BF16, "linear_fwd_droppath: bad dtype %d", dtype);
+  VITMI_CHECK_ARG(x && w && y && residual, "linear_fwd_droppath: null pointer");
+  VITMI_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "linear_fwd_droppath: negative size");
+  VITMI_CHECK_ARG(rows_per_sample >= 1, "linear_fwd_droppath: rows_per_sample must be >= 1 (got %lld)",
+                  (long long)rows_per_sample);
+  VITMI_CHECK_ARG(M % rows_per_sample == 0, "linear_fwd_droppath: M = %lld is not a multiple of rows_per_sample = %lld",
+                  (long long)M, (long long)rows_per_sample);
+  VITMI_CHECK_ARG(path_map_exact(M, rows_per_sample), "linear_fwd_droppath: M * rows_per_sample must be <= 2^32 "
+                  "(the row -> sample mapping is exact only there)");
+  GemmArgs d{};
+  d.drop_seed = seed; d.drop_site = drop_site; d.drop_thresh = drop_thresh; d.drop_scale = drop_scale;
+  d.path_site = path_site; d.path_thresh = path_thresh; d.path_scale = path_scale;
+  d.path_S = (uint32_t)rows_per_sample; d.path_magic = path_magic((uint32_t)rows_per_sample);
+  // drop_thresh 0 keeps every element: the path-only epilogue, no element hash
+  const int epi = drop_thresh ? EPI_RESIDUAL_DROP_PATH : EPI_RESIDUAL_PATH;
+  return gemm_impl(dtype, 1, 1, M, N, K, x, K, w, K, y, N, y_dtype, epi, bias, nullptr, N, residual, N,
                    workspace, ws_bytes, (hipStream_t)stream, false, &d);
 }
 

@@ -19,4 +19,7 @@ def __getattr__(name):
     if name in ("losses", "augment"):
         import importlib
         return importlib.import_module("." + name, __name__)
+    if name == "DropPath":   # the stochastic-depth module (vitmi.modules), same lazy import
+        from .modules import DropPath
+        return DropPath
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

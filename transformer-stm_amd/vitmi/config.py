@@ -59,6 +59,20 @@ class ViTConfig:
     # None = the knob's default: split for 'bf16x3', "weight" for 'bf16f8' (plain where
     # embed_dim % 128 != 0).  vitmi/modules.py Block.split_qkv
     split_qkv: "bool | str | None" = None
+    # stochastic depth (old_codes/MS_CvT.py Block.forward: x + drop_path(branch); the spec's
+    # DROP_PATH_RATE): in training each sample's attention branch and MLP branch of block i are
+    # dropped with probability linspace(0, drop_path_rate, depth)[i] and the kept ones scaled by
+    # 1/(1-p) (DeiT: 0.1 for ViT-B).  0 = off.
+    drop_path_rate: float = 0.0
+
+    def __post_init__(self):
+        if not 0.0 <= self.drop_path_rate < 1.0:   # (also refuses NaN)
+            raise ValueError(f"drop_path_rate must be in [0, 1) (got {self.drop_path_rate})")
+
+    def drop_path_rates(self) -> list:
+        """Per-block drop-path rate: linspace(0, drop_path_rate, depth), block 0 = 0 (MS_CvT, timm)."""
+        L, r = self.depth, float(self.drop_path_rate)
+        return [r * i / (L - 1) if L > 1 else 0.0 for i in range(L)]
 
     @property
     def grid(self) -> int:

@@ -49,16 +49,34 @@ _LP_ATTR = "_vitmi_lp"
 LP_STATS = {"hit": 0, "miss": 0}     # test hook: how often the handed-over copy was used
 
 
-def _drop_args(mod: nn.Module, rate: float, site0: int):
-    """(seed, rate, site0) for a training-mode forward with dropout, else None.  The seed is
-    ``mod.drop_seed`` when set (parity tests), otherwise drawn from torch's default CPU
-    generator, so ``torch.manual_seed`` makes the masks reproducible."""
-    if not mod.training or rate <= 0.0 or not torch.is_grad_enabled():
+# first drop-path site: block i uses _PATH_SITE0 + 2 i (attention branch) and + 2 i + 1 (MLP branch),
+# disjoint from the dropout sites 3 i .. 3 i + 2
+_PATH_SITE0 = 0x40000000
+
+
+def _drop_seed(mod: nn.Module, active: bool) -> Optional[int]:
+    """The mask seed of a training-mode forward that drops something (``active``), else None.  It
+    is ``mod.drop_seed`` when set (parity tests), otherwise drawn from torch's default CPU
+    generator, so ``torch.manual_seed`` makes the masks reproducible; nothing is drawn when
+    nothing drops."""
+    if not mod.training or not active or not torch.is_grad_enabled():
         return None
     seed = getattr(mod, "drop_seed", None)
     if seed is None:
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-    return (int(seed), float(rate), site0)
+    return int(seed)
+
+
+def _drop_args(mod: nn.Module, rate: float, site0: int):
+    """(seed, rate, site0) for a training-mode forward with dropout, else None (_drop_seed)."""
+    seed = _drop_seed(mod, rate > 0.0)
+    return None if seed is None else (seed, float(rate), site0)
+
+
+def _block_drop(seed: Optional[int], rate: float, i: int, path_rate: float):
+    """_BlockFn's ``drop`` of block i: (seed, dropout rate, first dropout site, drop-path rate,
+    first drop-path site), or None when the forward drops nothing anywhere."""
+    return None if seed is None else (seed, float(rate), 3 * i, float(path_rate), _PATH_SITE0 + 2 * i)
 
 
 def _sink(ctx, first: int, params, arena=None, extra=()) -> GradSink:
@@ -305,6 +323,54 @@ class _MlpFn(torch.autograd.Function):
         return (dx.view(ctx.shape), None) + gs.grads(ps)
 
 
+# ======================================================================= drop path
+class DropPath(nn.Module):
+    """Stochastic depth for user-built residual stacks, ``x + drop_path(branch(x))`` (MS_CvT.py
+    DropPath / timm): in training each sample of ``x`` ([B, S, D] or [B, D]) is zeroed with
+    probability ``rate`` and the kept ones scaled by 1 / (1 - rate); identity in eval mode or at
+    rate 0.  The keep decisions are the C ABI's pure hash of (seed, site, sample)
+    (vitmi_droppath_apply), regenerated in the backward.  ``drop_seed``: a fixed seed (tests;
+    None = one draw from torch's CPU generator per forward); ``site``: the mask stream, give
+    each DropPath of a model its own."""
+
+    def __init__(self, rate: float = 0.0):
+        super().__init__()
+        if not 0.0 <= rate < 1.0:
+            raise ValueError(f"DropPath rate must be in [0, 1) (got {rate})")
+        self.rate = float(rate)
+        self.drop_seed: Optional[int] = None
+        self.site = _PATH_SITE0
+
+    def forward(self, x: Tensor) -> Tensor:
+        seed = _drop_seed(self, self.rate > 0.0)
+        if seed is None:
+            return x
+        _check_cuda(x)
+        if x.dim() not in (2, 3):
+            raise ValueError("vitmi DropPath takes [B, S, D] or [B, D]")
+        return _DropPathFn.apply(x, seed, int(self.site), self.rate)
+
+    def extra_repr(self) -> str:
+        return f"rate={self.rate}"
+
+
+class _DropPathFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, seed, site, rate):
+        ctx.args = (seed, site, rate, 1 if x.dim() == 2 else x.shape[1])
+        return _DropPathFn._apply(x, ctx.args)
+
+    @staticmethod
+    def _apply(t, args):
+        seed, site, rate, S = args
+        t2 = t.contiguous().float()
+        return ops.droppath_apply(t2.view(-1, t2.shape[-1]), seed, site, rate, S, F32).view(t.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _DropPathFn._apply(dy, ctx.args), None, None, None
+
+
 # ======================================================================= block
 class Block(nn.Module):
     """Pre-LN transformer block ``x += Attn(LN1(x)); x += MLP(LN2(x))``
@@ -332,6 +398,7 @@ class Block(nn.Module):
         self.split_qkv = True if dtype == "bf16x3" else ("weight" if dtype == "bf16f8" and dim % 128 == 0 else False)
         self.eps = eps
         self.drop_rate = 0.0     # set by VisionTransformer / the caller (Keras default 0.1)
+        self.drop_path = 0.0     # stochastic depth of both branches (VisionTransformer: its linspace rate)
         self.drop_seed: Optional[int] = None   # fixed seed (tests); None = drawn per forward
 
     @property
@@ -340,8 +407,9 @@ class Block(nn.Module):
 
     def forward(self, x: Tensor, h: Optional[int] = None, w: Optional[int] = None) -> Tensor:
         _check_cuda(x)
-        return _BlockFn.apply(x, self, None, False, _drop_args(self, self.drop_rate, 0), _is_vitmi_node(x),
-                              *self.parameters())
+        seed = _drop_seed(self, self.drop_rate > 0.0 or self.drop_path > 0.0)
+        return _BlockFn.apply(x, self, None, False, _block_drop(seed, self.drop_rate, 0, self.drop_path),
+                              _is_vitmi_node(x), *self.parameters())
 
 
 class _BlockFn(torch.autograd.Function):
@@ -350,10 +418,14 @@ class _BlockFn(torch.autograd.Function):
     gradient).  ``prev_fc2_bias``: the fc2 bias of the block feeding this one; its gradient is
     colsum(d input), produced for free by this block's LN1 backward and returned for that input.
     ``fc2_bias_done``: this block's own fc2 bias gradient is supplied by its consumer (next block
-    or head).  ``drop``: (seed, rate, site0) -> training-mode dropout
-    (models/CvT(Par).py:189,255,257) at sites site0 (out-projection), site0+1 (GELU output),
-    site0+2 (fc2), fused into the GEMM epilogues; the backward regenerates the masks
-    (vitmi_dropout_apply)."""
+    or head).  ``drop``: (seed, rate, site0, path_rate, path_site0) (_block_drop) -> training-mode
+    dropout (models/CvT(Par).py:189,255,257) at sites site0 (out-projection), site0+1 (GELU output),
+    site0+2 (fc2), and stochastic depth (MS_CvT.py Block.forward) at sites path_site0 (attention
+    branch) and path_site0+1 (MLP branch): each sample's branch times its factor, after the element
+    dropout.  Both are fused into the GEMM epilogues; the backward regenerates the masks
+    (vitmi_dropout_apply / vitmi_droppath_apply, one pass per branch).  A non-None ``drop`` with both
+    rates 0 is a block that drops nothing inside a model that does: plain epilogues, but none of the
+    cross-block bias-gradient shortcuts or gradient handovers."""
 
     @staticmethod
     def forward(ctx, x, blk, prev_fc2_bias, fc2_bias_done, drop, handover, *params):
@@ -376,15 +448,19 @@ class _BlockFn(torch.autograd.Function):
         h1, m1, r1 = ops.layernorm_fwd(x2, n1.weight, n1.bias, blk.eps, T)
         qkv = ops.linear_fwd(h1, wq, a_.qkv.bias, T)
         o, lse = ops.attention_fwd(qkv, B, N, H, a_.scale)
-        dr = [None, None, None]
+        dr, dp = [None, None, None], [None, None]
         if drop is not None:
-            seed, rate, site0 = drop
-            dr = [(seed, site0 + j, rate) for j in range(3)]
-        x1 = ops.linear_fwd(o, wo, a_.proj.bias, F32, ops.EPI_RESIDUAL, residual=x2, dropout=dr[0])
+            seed, rate, site0, prate, psite0 = drop
+            if rate > 0:
+                dr = [(seed, site0 + j, rate) for j in range(3)]
+            if prate > 0:   # a sample is its N rows
+                dp = [(seed, psite0 + j, prate, N) for j in range(2)]
+        x1 = ops.linear_fwd(o, wo, a_.proj.bias, F32, ops.EPI_RESIDUAL, residual=x2, dropout=dr[0], droppath=dp[0])
         h2, m2, r2 = ops.layernorm_fwd(x1, n2.weight, n2.bias, blk.eps, T)
         # gelu' stays in the tile-native layout between fc1's epilogue and fc2's dgrad (bf16)
         act, u = ops.linear_fwd(h2, w1, blk.mlp.fc1.bias, T, ops.EPI_BIAS_GELU, dropout=dr[1], aux_tiled=T != F32)
-        out = ops.linear_fwd(act, w2, blk.mlp.fc2.bias, F32, ops.EPI_RESIDUAL, residual=x1, dropout=dr[2])
+        out = ops.linear_fwd(act, w2, blk.mlp.fc2.bias, F32, ops.EPI_RESIDUAL, residual=x1, dropout=dr[2],
+                             droppath=dp[1])
         ctx.save_for_backward(x2, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, u, act, wq, wo, w1, w2)
         return out.view(B, N, D)
 
@@ -410,7 +486,8 @@ class _BlockFn(torch.autograd.Function):
         sq = blk.split_qkv is True
         wq8 = f8 and blk.split_qkv == "weight" and D % 128 == 0
         if drop is not None:
-            raise ValueError(f"vitmi: dtype '{blk.dtype}' is the parity / evaluation knob; dropout is not supported")
+            raise ValueError(f"vitmi: dtype '{blk.dtype}' is the parity / evaluation knob; dropout and drop path "
+                             "are not supported")
         n1, n2 = blk.norm1, blk._norm2
         a_, mlp = blk.attn, blk.mlp
         split = ops.split_bf16f8 if f8 else ops.split_bf16x3
@@ -468,13 +545,15 @@ class _BlockFn(torch.autograd.Function):
         gs = _sink(ctx, 6, ps, getattr(blk, "_arena", None), extra=[(2, prev)] if prev is not None else [])
         g2 = dout.contiguous().float().view(M, D)
         drop = ctx.drop
-        if drop is None:
+        # this block's own branches were masked (element dropout and / or a sample factor)
+        masked = drop is not None and (drop[1] > 0 or drop[3] > 0)
+        if not masked:
             g2_lp = _take_lp(g2, T, dout)
         else:
-            # the fc2 branch was dropped: its dgrad/wgrad/bias see g2 * mask / (1 - p)
+            # the fc2 branch was dropped: its dgrad/wgrad/bias see g2 * mask / (1 - p) [* sample factor]
             dout.__dict__.pop(_LP_ATTR, None)
-            seed, rate, site0 = drop
-            g2_lp = ops.dropout_apply(g2, seed, site0 + 2, rate, T)
+            seed, rate, site0, prate, psite0 = drop
+            g2_lp = _branch_grad(g2, seed, site0 + 2, rate, psite0 + 1, prate, N, T)
         # the block's weight gradients, grouped per ops.WGRAD_GROUP (default: the out-projection's
         # and qkv's in one split-K launch over both outputs' tiles and one reduction, at qkv's
         # point; the MLP pair where du has just been written)
@@ -494,7 +573,7 @@ class _BlockFn(torch.autograd.Function):
             wg = []
         dh2 = ops.linear_dgrad(du, w1, T)
         # LN2 backward + residual; its column sums of dx1 are the out-proj bias grad
-        if drop is None:
+        if not masked:
             dx1, dx1_lp = ops.layernorm_bwd(dh2, x1, m2, r2, n2.weight, gs(n2.weight), gs(n2.bias),
                                             dres=g2, lp_dtype=lpT, dxsum=gs(a_.proj.bias))
             if dx1_lp is None:
@@ -502,7 +581,7 @@ class _BlockFn(torch.autograd.Function):
         else:
             dx1, _ = ops.layernorm_bwd(dh2, x1, m2, r2, n2.weight, gs(n2.weight), gs(n2.bias),
                                        dres=g2, lp_dtype=None)
-            dx1_lp = ops.dropout_apply(dx1, seed, site0, rate, T)
+            dx1_lp = _branch_grad(dx1, seed, site0, rate, psite0, prate, N, T)
             if gs.wants(a_.proj.bias):
                 ops.bias_grad(dx1_lp, gs(a_.proj.bias))
         # attention branch
@@ -529,6 +608,16 @@ class _BlockFn(torch.autograd.Function):
         wr.join()
         out = _handover(dx.view(B, N, D), dx_lp)
         return (out, None, gs.grads([prev])[0], None, None, None) + gs.grads(ps)
+
+
+def _branch_grad(g: Tensor, seed: int, dsite: int, drate: float, psite: int, prate: float, S: int,
+                 T: torch.dtype) -> Tensor:
+    """``g`` (fp32 [M, D]) as the gradient entering a branch that the forward masked: times the
+    element-dropout mask of (dsite, drate) and / or the drop-path factor of (psite, prate) of each
+    S-row sample, in the compute dtype; one launch either way."""
+    if prate > 0:
+        return ops.droppath_apply(g, seed, psite, prate, S, T, dropout=(dsite, drate))
+    return ops.dropout_apply(g, seed, dsite, drate, T)
 
 
 # the block backward's weight gradients on a side stream (VITMI_WGRAD_STREAM=0: the current one).
@@ -879,6 +968,8 @@ class VisionTransformer(nn.Module):
         if cfg.split_qkv is not None:
             for blk in self.blocks:
                 blk.split_qkv = cfg.split_qkv
+        for blk, r in zip(self.blocks, cfg.drop_path_rates()):   # stochastic depth: linspace over depth
+            blk.drop_path = r
         self.norm = LayerNorm(D, cfg.ln_eps)
         self.head = Linear(D, cfg.num_classes)
         self._arena: Optional[ParamArena] = None
@@ -944,14 +1035,16 @@ class VisionTransformer(nn.Module):
         t = _EmbedFn.apply(x, pe, self.cls_token, self.pos_embed, *pe.parameters())
         # bias-grad fusion: block i's LN1 backward produces colsum(d input) = the fc2 bias grad
         # of block i-1; the head's LN backward does it for the last block.
-        drop = _drop_args(self, self.cfg.drop_rate, 0)
-        # with dropout the fc2/proj bias grads are column sums of MASKED gradients: no fusion
-        self._fc2_bias_fused = drop is None
+        rate = self.cfg.drop_rate
+        seed = _drop_seed(self, rate > 0.0 or any(blk.drop_path > 0.0 for blk in self.blocks))
+        # with dropout or drop path the fc2/proj bias grads are column sums of MASKED gradients: no
+        # fusion across blocks, in any block of the model
+        fused = self._fc2_bias_fused = seed is None
         L = len(self.blocks)
         for i, blk in enumerate(self.blocks):
-            prev_bias = self.blocks[i - 1].mlp.fc2.bias if i > 0 and drop is None else None
-            done = drop is None and (i < L - 1 or _head_takes_bias)
-            d = None if drop is None else (drop[0], drop[1], 3 * i)
+            prev_bias = self.blocks[i - 1].mlp.fc2.bias if i > 0 and fused else None
+            done = fused and (i < L - 1 or _head_takes_bias)
+            d = _block_drop(seed, rate, i, blk.drop_path)
             # block 0's input gradient goes to the patch embedding's backward, which reads fp32
             t = _BlockFn.apply(t, blk, prev_bias, done, d, i > 0, *blk.parameters())
         return t
@@ -966,6 +1059,6 @@ def build_model(cfg: ViTConfig, device="cuda") -> VisionTransformer:
     return VisionTransformer(cfg).to(device)
 
 
-__all__ = ["LayerNorm", "Linear", "Attention", "Mlp", "Block", "ConvEmbed", "VisionTransformer",
+__all__ = ["LayerNorm", "Linear", "Attention", "Mlp", "Block", "DropPath", "ConvEmbed", "VisionTransformer",
            "cross_entropy", "mse_loss", "build_model", "ParamArena"]
 

@@ -118,11 +118,16 @@ def dropout_params(p: float):
 
 def linear_fwd(x: Tensor, w: Tensor, bias: Optional[Tensor], out_dtype: torch.dtype,
                epilogue: int = EPI_STORE, residual: Optional[Tensor] = None, dropout=None,
-               aux_tiled: bool = False, split_x3: bool = False, f8=False, split_f8: bool = False):
+               aux_tiled: bool = False, split_x3: bool = False, f8=False, split_f8: bool = False,
+               droppath=None):
     """y = x W^T + b (+GELU, +residual).  x [M,K], w [N,K] (same dtype).  Returns y
     (and gelu'(pre-activation), the saved GELU derivative, for EPI_BIAS_GELU).
     ``dropout`` = (seed, site, rate) fuses the dropout of the GELU output / of the branch
     before the residual add into the epilogue (vitmi_linear_fwd_dropout).
+    ``droppath`` = (seed, site, rate, rows_per_sample) (EPI_RESIDUAL): the branch of every sample
+    (rows_per_sample consecutive rows) is scaled by its drop-path factor before the residual add,
+    after ``dropout`` when both are given (same seed; vitmi_linear_fwd_droppath).  Rate 0 is the
+    plain epilogue.
     ``aux_tiled`` (bf16): gelu' comes back as an opaque buffer in the tile-native layout, for a
     linear_dgrad(..., EPI_DGELU, aux_tiled=True) of the same [M, N].
     ``split_x3`` (EPI_BIAS_GELU, bf16): y is [M, 3N], each row [hi | hi | lo] of the fp32 GELU
@@ -166,7 +171,19 @@ def linear_fwd(x: Tensor, w: Tensor, bias: Optional[Tensor], out_dtype: torch.dt
     xdt = BF16F8W_DT if f8w else BF16F8_DT if f8 else dt(x.dtype)
     nws = lib().vitmi_linear_fwd_workspace_size(xdt, M, N, K)
     ws = _ws(nws, x) if nws else None
-    if dropout is not None and dropout[2] > 0:
+    if droppath is not None and droppath[2] > 0:
+        assert epilogue == EPI_RESIDUAL and not f8, "droppath: the RESIDUAL epilogue of a bf16 / fp32 GEMM"
+        seed, psite, prate, rps = droppath
+        pthresh, pscale = dropout_params(prate)
+        dsite, dthresh, dscale = 0, 0, 1.0          # (thresh 0: no element dropout)
+        if dropout is not None and dropout[2] > 0:
+            assert dropout[0] == seed, "droppath and dropout share the forward's seed"
+            dsite = dropout[1]
+            dthresh, dscale = dropout_params(dropout[2])
+        check(lib().vitmi_linear_fwd_droppath(dt(x.dtype), M, N, K, _p(x), _p(w), _p(bias), _p(y), dt(out_dtype),
+                                              epilogue, _p(residual), _p(ws), nws, seed & 0xFFFFFFFF, dsite, dthresh,
+                                              dscale, rps, psite, pthresh, pscale, _s()), "linear_fwd_droppath")
+    elif dropout is not None and dropout[2] > 0:
         seed, site, rate = dropout
         thresh, scale = dropout_params(rate)
         check(lib().vitmi_linear_fwd_dropout(dt(x.dtype), M, N, K, _p(x), _p(w), _p(bias), _p(y),
@@ -190,6 +207,25 @@ def dropout_apply(x: Tensor, seed: int, site: int, rate: float, out_dtype: torch
     thresh, scale = dropout_params(rate)
     check(lib().vitmi_dropout_apply(M, N, _p(x), ldx, _p(y), dt(out_dtype), N, seed & 0xFFFFFFFF, site,
                                     thresh, scale, _s()), "dropout_apply")
+    return y
+
+
+def droppath_apply(x: Tensor, seed: int, site: int, rate: float, rows_per_sample: int, out_dtype: torch.dtype,
+                   dropout=None) -> Tensor:
+    """x (fp32, rows x C) * f[row // rows_per_sample], f = the drop-path factor (0 or 1 / (1 - rate))
+    of the row's sample at ``site``, in out_dtype: the gradient entering a branch whose forward was
+    scaled by the same factor.  ``dropout`` = (site, rate): also times that site's element-dropout
+    mask (same seed), in the same launch (vitmi_droppath_apply)."""
+    M, ldx = _rows(x)
+    N = x.shape[-1]
+    y = torch.empty(M, N, dtype=out_dtype, device=x.device)
+    pthresh, pscale = dropout_params(rate)
+    dsite, dthresh, dscale = 0, 0, 1.0
+    if dropout is not None and dropout[1] > 0:
+        dsite = dropout[0]
+        dthresh, dscale = dropout_params(dropout[1])
+    check(lib().vitmi_droppath_apply(M, N, _p(x), ldx, _p(y), dt(out_dtype), N, rows_per_sample, seed & 0xFFFFFFFF,
+                                     site, pthresh, pscale, dsite, dthresh, dscale, _s()), "droppath_apply")
     return y
 
 
