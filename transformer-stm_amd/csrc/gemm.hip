@@ -71,7 +71,7 @@ struct GemmArgs {
   const float* residual;
   int64_t ldr;
   int64_t k_per_split;   // reduction range of one blockIdx.z (multiple of BK)
-  int64_t split_stride;  // elements between split partial slabs (EPI_PARTIAL)
+  int64_t split_stride;  // elements between split partial slabs (EpiPartial)
   int tiles_n;           // number of BN tiles along N
   // gemm256 tail split (stream-K-like): units [0, t_full) are whole tiles; the remaining
   // tiles are split into nsplit K-ranges of ksplit K-steps each, written as fp32 partials
@@ -81,14 +81,14 @@ struct GemmArgs {
   int ksplit;
   float* tail_ws;
   size_t tail_ws_bytes;
-  // gemm256 split-K folded into the persistent unit space (EPI_PARTIAL): unit = z*ntiles +
+  // gemm256 split-K folded into the persistent unit space (EpiPartial): unit = z*ntiles +
   // tile, slab z covers K-steps [z*kz_steps, (z+1)*kz_steps).  Consecutive units share one
   // K-range, so the contiguous unit range of an XCD re-reads its A/B panels from that
   // XCD's L2 (a gridDim.z split scatters them over all XCDs).
   int kz;          // 1 = no folded split
   int kz_steps;
   int ntiles;
-  // dropout of the *_DROP epilogues (see drop_hash in common.h)
+  // dropout of the dropping epilogues, Epi::drop (see drop_hash in common.h)
   uint32_t drop_seed, drop_site, drop_thresh;
   float drop_scale;
   // gemm256 DGELU epilogue: column sums of the output (the bias gradient of the layer whose
@@ -99,7 +99,7 @@ struct GemmArgs {
   // VITMI_BF16F8 operands (gemm256<..., F8>): K-steps >= k8 (absolute, 64-bf16 = 128-B steps) are
   // the rows' e4m3 parts, multiplied by the block-scaled fp8 MFMA; the steps before are bf16
   int k8;
-  // grouped weight gradients (gemm256_kernel<false, false, EPI_PARTIAL, float, false, true>): up to
+  // grouped weight gradients (gemm256_kernel<false, false, EpiPartial, float, false, true>): up to
   // GRP_MAX problems over one reduction length K, each with its own operands and partial slabs;
   // the folded split-K unit space runs over their concatenated tiles (problem p owns tiles
   // [tile0, tile0 + tiles)); slab z of problem p at C + z * M * N (fp32, row pitch N)
@@ -111,9 +111,9 @@ struct GemmArgs {
     int tiles_n, tile0;
   } grp[4];
   int ngrp;
-  // stochastic depth of the *_PATH residual epilogues: row r belongs to sample r / path_S, and the
-  // whole sample is kept iff drop_hash(drop_row_key(drop_seed, path_site, sample), 0) >= path_thresh
-  // (factor path_scale, else 0).  path_magic: path_sample() in common.h
+  // stochastic depth of the path-dropping residual epilogues (Epi::path): row r belongs to sample
+  // r / path_S, and the whole sample is kept iff drop_hash(drop_row_key(drop_seed, path_site, sample), 0)
+  // >= path_thresh (factor path_scale, else 0).  path_magic: path_sample() in common.h
   uint32_t path_site, path_thresh, path_S, path_magic;
   float path_scale;
 };
@@ -160,25 +160,85 @@ __device__ __forceinline__ void tile_rc(const GemmArgs& g, int tl, int& tm, int&
   }
 }
 
-// internal epilogues: split-K partial slab, and GELU / residual with a fused dropout
-// EPI_GELU_X3: BIAS_GELU with the activation written split, [hi | hi | lo] (VITMI_EPI_SPLIT_X3)
-// EPI_GELU_F8: BIAS_GELU with the activation written as VITMI_BF16F8 A-operand rows (VITMI_EPI_SPLIT_F8)
-// EPI_RESIDUAL_PATH: RESIDUAL with the branch scaled by its sample's drop-path factor;
-// EPI_RESIDUAL_DROP_PATH: the element dropout of RESIDUAL_DROP first, then the sample factor
-enum { EPI_PARTIAL = 100, EPI_GELU_DROP = 101, EPI_RESIDUAL_DROP = 102, EPI_GELU_X3 = 103, EPI_GELU_F8 = 104,
-       EPI_RESIDUAL_PATH = 105, EPI_RESIDUAL_DROP_PATH = 106 };
-// the public epilogue an internal one extends, whether it drops elements and whether it drops paths
-template <int EPI> struct EpiOf {
-  static constexpr bool path = EPI == EPI_RESIDUAL_PATH || EPI == EPI_RESIDUAL_DROP_PATH;
-  static constexpr int base = EPI == EPI_GELU_DROP || EPI == EPI_GELU_X3 || EPI == EPI_GELU_F8 ? VITMI_EPI_BIAS_GELU
-                              : EPI == EPI_RESIDUAL_DROP || path ? VITMI_EPI_RESIDUAL : EPI;
-  static constexpr bool drop = EPI == EPI_GELU_DROP || EPI == EPI_RESIDUAL_DROP || EPI == EPI_RESIDUAL_DROP_PATH;
+// ---- epilogue descriptors ----------------------------------------------------
+// An epilogue is a type, Epi<public base, element dropout, drop path, output split, split-K partial>;
+// every property that a kernel or the host launch reads about it is a member below, defined once.
+// Its integer `code` exists only between the extern "C" entry points and the dispatch table (`dispatch`):
+// the public VITMI_EPI_* value in the low 3 bits (so `code & 7` is the base), the rest above them.
+enum { LD_NONE, LD_AUX, LD_RESIDUAL, LD_C };   // what an epilogue loads: nothing, bf16 gelu', fp32 residual, fp32 C
+enum { SPLIT_NONE, SPLIT_X3, SPLIT_F8 };       // how the activation is written (VITMI_EPI_SPLIT_X3 / _F8)
+template <int BASE, bool DROP = false, bool PATH = false, int SPLIT = SPLIT_NONE, bool PARTIAL = false>
+struct Epi {
+  static constexpr int base = BASE;           // the public epilogue this one is or extends
+  static constexpr int code = BASE | PARTIAL << 3 | DROP << 4 | PATH << 5 | SPLIT << 6;
+  // element dropout (GemmArgs::drop_*); drop path: a factor per sample (GemmArgs::path_*); the raw fp32
+  // slab of a split-K ACCUM, summed by a reduce kernel
+  static constexpr bool drop = DROP, path = PATH, partial = PARTIAL;
+  static constexpr int split = SPLIT;
+  static constexpr bool plain = !DROP && !PATH && SPLIT == SPLIT_NONE && !PARTIAL;
+  static constexpr bool has_bias = BASE == VITMI_EPI_STORE || BASE == VITMI_EPI_BIAS_GELU || BASE == VITMI_EPI_RESIDUAL;
+  static constexpr int loads = PARTIAL ? LD_NONE : BASE == VITMI_EPI_DGELU ? LD_AUX
+                               : BASE == VITMI_EPI_RESIDUAL ? LD_RESIDUAL : BASE == VITMI_EPI_ACCUM ? LD_C : LD_NONE;
+  static constexpr bool second_out = BASE == VITMI_EPI_BIAS_GELU;   // gelu' into aux
+  // bytes per element of C for the output type TC (residual / accumulate / partial are fp32 whatever TC)
+  template <typename TC>
+  static constexpr int ces = sizeof(TC) == 2 && BASE != VITMI_EPI_RESIDUAL && BASE != VITMI_EPI_ACCUM ? 2 : 4;
+  // Vector-memory ops that gemm256's epilogue issues per tile and wave.  bf16 outputs: 2 stores per
+  // 16-row group and output image (C, + gelu', the split forms' extra copies of C); fp32 outputs: 32
+  // direct stores; + 16 aux loads for DGELU, + 32 loads for residual / accumulate.  (DGELU's 4
+  // column-sum stores only make the waits stricter.)  The first K-step after an epilogue that
+  // issued S ops waits for vmcnt 8 + S (capped at the counter's 63): S = 16 (bf16 store), 32 (GELU,
+  // fp32 store, split partials), 48 (DGELU to fp32, SPLIT_F8), 64 (residual / accumulate, SPLIT_X3).
+  // An op issued after the awaited DMA stays outstanding while it does (in-order completion), so
+  // 8 + S is the loosest exact wait (WAITF in gemm256_kernel).
+  template <typename TC>
+  static constexpr int vmem_ops = (ces<TC> == 2 ? 16 * ((SPLIT == SPLIT_X3 ? 3 : SPLIT == SPLIT_F8 ? 2 : 1) + second_out) : 32) +
+                                  (loads == LD_AUX ? 16 : loads != LD_NONE ? 32 : 0);
+  // gemm256's tail split.  Measured: it pays off for long reductions (>= `mink` = VITMI_TAIL_MINK
+  // K-steps) and at any length for the DGELU epilogue (whose partial units skip its aux loads); a
+  // wash or a loss for K = 768 otherwise.  Accumulating epilogues never split (their K-slabs fill the
+  // chip), and SPLIT_F8 tiles stay whole: the fix-up kernel does not write the split-f8 rows.
+  static constexpr bool tail_split = BASE != VITMI_EPI_ACCUM && SPLIT != SPLIT_F8;
+  static constexpr int tail_min_ksteps(int mink) { return BASE == VITMI_EPI_DGELU ? 0 : mink; }
+  // Algorithmic bytes beside the operands (gemm_stat): C written once (read too for ACCUM: the += of
+  // a weight gradient, fp32), plus the epilogue's aux / residual.  mn = M N, es = operand element size
+  template <typename TC>
+  static double stat_bytes(double mn, double es) {
+    double b = BASE == VITMI_EPI_ACCUM ? 2.0 * mn * 4 : mn * sizeof(TC) * (SPLIT == SPLIT_X3 ? 3 : 1);
+    if (BASE == VITMI_EPI_BIAS_GELU || BASE == VITMI_EPI_DGELU) b += mn * es;   // gelu' written / read
+    if (BASE == VITMI_EPI_RESIDUAL) b += mn * 4;                                 // residual read
+    return b;
+  }
+  // The 128x128 kernel's swapped-operand store path: bf16 outputs of the store / GELU / DGELU
+  // epilogues (see gemm_kernel)
+  template <typename T, typename TC>
+  static constexpr bool swp = std::is_same<T, bf16>::value && std::is_same<TC, bf16>::value && plain &&
+                              (BASE == VITMI_EPI_STORE || BASE == VITMI_EPI_BIAS_GELU || BASE == VITMI_EPI_DGELU);
 };
-static inline int epi_base(int epi) {
-  return epi == EPI_GELU_DROP || epi == EPI_GELU_X3 || epi == EPI_GELU_F8 ? VITMI_EPI_BIAS_GELU
-         : epi == EPI_RESIDUAL_DROP || epi == EPI_RESIDUAL_PATH || epi == EPI_RESIDUAL_DROP_PATH ? VITMI_EPI_RESIDUAL
-         : epi;
+using EpiStore = Epi<VITMI_EPI_STORE>;
+using EpiGelu = Epi<VITMI_EPI_BIAS_GELU>;
+using EpiResidual = Epi<VITMI_EPI_RESIDUAL>;
+using EpiDgelu = Epi<VITMI_EPI_DGELU>;
+using EpiAccum = Epi<VITMI_EPI_ACCUM>;
+using EpiPartial = Epi<VITMI_EPI_ACCUM, false, false, SPLIT_NONE, true>;
+using EpiGeluDrop = Epi<VITMI_EPI_BIAS_GELU, true>;
+// BIAS_GELU with the activation written split, [hi | hi | lo] / as VITMI_BF16F8 A-operand rows
+using EpiGeluX3 = Epi<VITMI_EPI_BIAS_GELU, false, false, SPLIT_X3>;
+using EpiGeluF8 = Epi<VITMI_EPI_BIAS_GELU, false, false, SPLIT_F8>;
+using EpiResidualDrop = Epi<VITMI_EPI_RESIDUAL, true>;
+// RESIDUAL with the branch scaled by its sample's drop-path factor; with both, the element dropout
+// first, then the sample factor
+using EpiResidualPath = Epi<VITMI_EPI_RESIDUAL, false, true>;
+using EpiResidualDropPath = Epi<VITMI_EPI_RESIDUAL, true, true>;
+// the public epilogue that a runtime code is or extends (a code that is none of these: itself)
+static int epi_base(int code) {
+  for (int c : {EpiStore::code, EpiGelu::code, EpiResidual::code, EpiDgelu::code, EpiAccum::code, EpiPartial::code,
+                EpiGeluDrop::code, EpiGeluX3::code, EpiGeluF8::code, EpiResidualDrop::code, EpiResidualPath::code,
+                EpiResidualDropPath::code})
+    if (c == code) return code & 7;
+  return code;
 }
+
 // dropout factor (0 or 1/(1-p)) of output element (row, col)
 __device__ __forceinline__ float drop_factor(const GemmArgs& g, int64_t row, int64_t col) {
   return drop_hash(drop_row_key(g.drop_seed, g.drop_site, (uint32_t)row), (uint32_t)col) >= g.drop_thresh
@@ -188,6 +248,29 @@ __device__ __forceinline__ float drop_factor(const GemmArgs& g, int64_t row, int
 __device__ __forceinline__ float path_factor(const GemmArgs& g, int64_t row) {
   return path_keep(g.drop_seed, g.path_site, path_sample((uint32_t)row, g.path_S, g.path_magic), g.path_thresh)
              ? g.path_scale : 0.f;
+}
+// The branch value of the bias-carrying epilogues, from ab = acc + bias: ab [x element keep] [x sample
+// factor], for one element and for the 4 columns col0 .. col0 + 3.  The 128x128 kernel (epi_store) and
+// the fix-up kernel form it here; gemm256's residual epilogue writes the same two steps out, because
+// its register allocation does not survive the call (see there).  Each site adds the residual itself.
+// With a factor that is one sum of two terms, the same in any order.  Plain RESIDUAL has no factor
+// and three terms, and the sites associate them differently: gemm256 rounds a whole tile as
+// (acc + bias) + residual, while the 128x128 kernel and the fix-up kernel (a tail tile of the same
+// GEMM) round (residual + acc) + bias.
+template <typename E>
+__device__ __forceinline__ float branch(const GemmArgs& g, float ab, int64_t row, int64_t col) {
+  if constexpr (E::drop) ab *= drop_factor(g, row, col);
+  if constexpr (E::path) ab *= path_factor(g, row);
+  return ab;
+}
+template <typename E>
+__device__ __forceinline__ f32x4 branch4(const GemmArgs& g, f32x4 ab, int64_t row, int64_t col0) {
+  if constexpr (E::drop) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ab[e] *= drop_factor(g, row, col0 + e);   // (the row's key is common)
+  }
+  if constexpr (E::path) ab *= path_factor(g, row);
+  return ab;
 }
 
 __device__ __forceinline__ int swz_k(int row) { return (row >> 1) & 7; }
@@ -335,48 +418,47 @@ __device__ __forceinline__ f32x4 mma(const Frag<float>& a, const Frag<float>& b,
 }
 
 // ---- epilogue ----------------------------------------------------------------
-template <typename T, typename TC, int EPI>
+template <typename T, typename TC, typename E>
 __device__ __forceinline__ void epi_store(const GemmArgs& g, int64_t row, int64_t col, float acc,
                                           float biasv) {
-  if constexpr (EPI == EPI_GELU_DROP) {
-    const float u = acc + biasv, f = drop_factor(g, row, col);
-    ((T*)g.aux)[aux_at(g, row, col)] = from_f32<T>(gelu_grad_f(u) * f);
-    ((TC*)g.C)[row * g.ldc + col] = from_f32<TC>(gelu_f(u) * f);
-  } else if constexpr (EPI == EPI_RESIDUAL_DROP) {
-    ((float*)g.C)[row * g.ldc + col] = g.residual[row * g.ldr + col] + (acc + biasv) * drop_factor(g, row, col);
-  } else if constexpr (EPI == EPI_RESIDUAL_PATH) {
-    ((float*)g.C)[row * g.ldc + col] = g.residual[row * g.ldr + col] + (acc + biasv) * path_factor(g, row);
-  } else if constexpr (EPI == EPI_RESIDUAL_DROP_PATH) {
-    ((float*)g.C)[row * g.ldc + col] =
-        g.residual[row * g.ldr + col] + (acc + biasv) * drop_factor(g, row, col) * path_factor(g, row);
-  } else if constexpr (EPI == EPI_PARTIAL) {
+  if constexpr (E::partial) {
     ((float*)g.C)[blockIdx.z * g.split_stride + row * g.ldc + col] = acc;
-  } else if constexpr (EPI == VITMI_EPI_STORE) {
+  } else if constexpr (E::split == SPLIT_F8) {
+    // (written by gemm256 alone; its tiles are never finished here, see Epi::tail_split)
+  } else if constexpr (E::base == VITMI_EPI_STORE) {
     ((TC*)g.C)[row * g.ldc + col] = from_f32<TC>(acc + biasv);
-  } else if constexpr (EPI == VITMI_EPI_BIAS_GELU) {
+  } else if constexpr (E::base == VITMI_EPI_BIAS_GELU) {
     const float u = acc + biasv;
-    ((T*)g.aux)[aux_at(g, row, col)] = from_f32<T>(gelu_grad_f(u));
-    ((TC*)g.C)[row * g.ldc + col] = from_f32<TC>(gelu_f(u));
-  } else if constexpr (EPI == EPI_GELU_X3) {
-    const float u = acc + biasv, a = gelu_f(u);
-    const bf16 hi = (bf16)a;
-    bf16* c = (bf16*)g.C + row * g.ldc + col;
-    ((T*)g.aux)[aux_at(g, row, col)] = from_f32<T>(gelu_grad_f(u));
-    c[0] = hi;
-    c[g.N] = hi;
-    c[2 * g.N] = (bf16)(a - (float)hi);
-  } else if constexpr (EPI == VITMI_EPI_RESIDUAL) {
-    ((float*)g.C)[row * g.ldc + col] = g.residual[row * g.ldr + col] + acc + biasv;
-  } else if constexpr (EPI == VITMI_EPI_DGELU) {
+    if constexpr (E::split == SPLIT_X3) {
+      const float a = gelu_f(u);
+      const bf16 hi = (bf16)a;
+      bf16* c = (bf16*)g.C + row * g.ldc + col;
+      ((T*)g.aux)[aux_at(g, row, col)] = from_f32<T>(gelu_grad_f(u));
+      c[0] = hi;
+      c[g.N] = hi;
+      c[2 * g.N] = (bf16)(a - (float)hi);
+    } else if constexpr (E::drop) {   // dropped: a = gelu(u) m/(1-p), aux = gelu'(u) m/(1-p)
+      const float f = drop_factor(g, row, col);
+      ((T*)g.aux)[aux_at(g, row, col)] = from_f32<T>(gelu_grad_f(u) * f);
+      ((TC*)g.C)[row * g.ldc + col] = from_f32<TC>(gelu_f(u) * f);
+    } else {
+      ((T*)g.aux)[aux_at(g, row, col)] = from_f32<T>(gelu_grad_f(u));
+      ((TC*)g.C)[row * g.ldc + col] = from_f32<TC>(gelu_f(u));
+    }
+  } else if constexpr (E::base == VITMI_EPI_RESIDUAL) {
+    const float r = g.residual[row * g.ldr + col];
+    if constexpr (E::drop || E::path) ((float*)g.C)[row * g.ldc + col] = r + branch<E>(g, acc + biasv, row, col);
+    else ((float*)g.C)[row * g.ldc + col] = r + acc + biasv;   // (see `branch`)
+  } else if constexpr (E::base == VITMI_EPI_DGELU) {
     const float gp = to_f32(((const T*)g.aux)[aux_at(g, row, col)]);
     ((TC*)g.C)[row * g.ldc + col] = from_f32<TC>(acc * gp);
-  } else if constexpr (EPI == VITMI_EPI_ACCUM) {
+  } else if constexpr (E::loads == LD_C) {
     ((float*)g.C)[row * g.ldc + col] += acc;
   }
 }
 
 // ---- the kernel ------------------------------------------------------------
-template <typename T, bool AK, bool BKM, int EPI, typename TC, int BM, int BN, int WM, int WN>
+template <typename T, bool AK, bool BKM, typename E, typename TC, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs g) {
   constexpr int ES = TT<T>::ES, BK = TT<T>::BK;
   constexpr int NW = WM * WN;
@@ -386,8 +468,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs g) {
   // bf16 outputs of the store / GELU / DGELU epilogues: MFMA operands swapped (C^T in the
   // accumulator, as in gemm256), so a lane owns 4 consecutive columns of one row and stores them
   // as one 8-byte vector instead of four 2-byte scalars (the CvT's K = 64 stage-1 MLP GEMMs)
-  constexpr bool SWP = std::is_same<T, bf16>::value && std::is_same<TC, bf16>::value &&
-                       (EPI == VITMI_EPI_STORE || EPI == VITMI_EPI_BIAS_GELU || EPI == VITMI_EPI_DGELU);
+  constexpr bool SWP = E::template swp<T, TC>;
   __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
 
   const int lane = threadIdx.x & 63;
@@ -471,7 +552,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs g) {
       if (col0 >= g.N) continue;
       float bv[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) bv[e] = (g.bias && EPI != VITMI_EPI_DGELU && col0 + e < g.N) ? g.bias[col0 + e] : 0.f;
+      for (int e = 0; e < 4; ++e) bv[e] = (g.bias && E::has_bias && col0 + e < g.N) ? g.bias[col0 + e] : 0.f;
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int64_t row = m0 + wm * (BM / WM) + i * 16 + rl;
@@ -481,9 +562,9 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs g) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const float v = acc[i][j][e];
-            if constexpr (EPI == VITMI_EPI_STORE) {
+            if constexpr (E::base == VITMI_EPI_STORE) {
               o[e] = (bf16)(v + bv[e]);
-            } else if constexpr (EPI == VITMI_EPI_BIAS_GELU) {
+            } else if constexpr (E::base == VITMI_EPI_BIAS_GELU) {
               const float u = v + bv[e];
               ((T*)g.aux)[aux_at(g, row, col0 + e)] = from_f32<T>(gelu_grad_f(u));
               o[e] = (bf16)gelu_f(u);
@@ -495,7 +576,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs g) {
         } else {
 #pragma unroll
           for (int e = 0; e < 4; ++e)
-            if (col0 + e < g.N) epi_store<T, TC, EPI>(g, row, col0 + e, acc[i][j][e], bv[e]);
+            if (col0 + e < g.N) epi_store<T, TC, E>(g, row, col0 + e, acc[i][j][e], bv[e]);
         }
       }
     }
@@ -508,14 +589,13 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs g) {
   for (int j = 0; j < TN; ++j) {
     const int64_t col = n0 + wn * (BN / WN) + j * 16 + cl;
     if (col >= g.N) continue;
-    const float bv = (g.bias && EPI != EPI_PARTIAL && EPI != VITMI_EPI_ACCUM &&
-                      EPI != VITMI_EPI_DGELU) ? g.bias[col] : 0.f;   // (the *_DROP ones have bias)
+    const float bv = (g.bias && E::has_bias) ? g.bias[col] : 0.f;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t row = m0 + wm * (BM / WM) + i * 16 + rg + r;
-        if (row < g.M) epi_store<T, TC, EPI>(g, row, col, acc[i][j][r], bv);
+        if (row < g.M) epi_store<T, TC, E>(g, row, col, acc[i][j][r], bv);
       }
     }
   }
@@ -652,17 +732,13 @@ __device__ __forceinline__ void gelu4(f32x4 x, f32x4& a, f32x4& gp) {
 // Waits: vmcnt(8) at P0 retires B1(s), at P1 A1(s), at P3 A0(s+1),B0(s+1); each sits
 // before a barrier that the later reader passes, with one barrier of slack for the
 // staggered group.
-template <bool AK, bool BKM, int EPI, typename TC, bool F8 = false, bool GRP = false>
+template <bool AK, bool BKM, typename E, typename TC, bool F8 = false, bool GRP = false>
 __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
   using namespace g256;
   // two DMA stages + the bias of the current and the next tile (fp32, double-buffered) + one
   // per-wave image of a 16-row group of the output, through which bf16 epilogue stores leave
   // as whole 128-B lines
   __shared__ __attribute__((aligned(16))) char smem[2 * STAGE + 2048 + NWAVES * EPI_SCR];
-  constexpr int EB = EpiOf<EPI>::base;         // public epilogue (the *_DROP ones extend one)
-  constexpr bool DROP = EpiOf<EPI>::drop;
-  constexpr bool PATH = EpiOf<EPI>::path;      // (the *_PATH ones: a factor per sample of path_S rows)
-  constexpr bool HAS_BIAS = EB == VITMI_EPI_STORE || EB == VITMI_EPI_BIAS_GELU || EB == VITMI_EPI_RESIDUAL;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 2, wn = wave & 3;
@@ -712,7 +788,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
     ks0_ = 0;
     nk_ = nk;
     z_ = 0;
-    if (EPI == EPI_PARTIAL && g.kz > 1) {
+    if (E::partial && g.kz > 1) {
       z_ = u / g.ntiles;
       tl = u - z_ * g.ntiles;
       ks0_ = z_ * g.kz_steps;
@@ -740,6 +816,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
     m0_ = (int64_t)tm_ * BM;
     n0_ = (int64_t)tn_ * BN;
   };
+  // the current unit is a K-range of a tail tile: its epilogue is the raw fp32 partial for
+  // gemm_tail_fixup_kernel (a macro: as a lambda or a local the EpiPartial kernels allocate differently)
+#define RAW_TAIL() ((!E::partial || g.kz <= 1) && tile >= g.t_full)
   auto sub = [&](int buf, int which) -> char* { return smem + buf * STAGE + which * HALF; };
   // issue half `which` (0=A0 1=B0 2=A1 3=B1) of K-step t into buffer buf
   // (la, lb: the row pitches of the unit the descriptors belong to; g's unless GRP)
@@ -866,7 +945,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
 #endif
   for (;;) {
     stamp(0);
-    if constexpr (HAS_BIAS) {
+    if constexpr (E::has_bias) {
       // bias[n0 .. n0+256) -> LDS by ONE LDS-DMA instruction of wave 0 (64 lanes x 16 B; the
       // range check zero-fills columns >= N and a null bias).  It is older than every DMA the
       // K-loop waits for, so it only makes those counted waits stricter; the epilogue reads it
@@ -884,10 +963,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
     const __amdgpu_buffer_rsrc_t ran = rsrc_a(m0n, ks0n, pn), rbn = rsrc_b(n0n, ks0n, pn);
     const int64_t lan = GRP ? g.grp[pn].lda : g.lda, lbn = GRP ? g.grp[pn].ldb : g.ldb;
 
-      // vmcnt counts of the first step after an epilogue that issued S vector-memory ops:
-      // 8 + S (capped at the counter's 63): S = 16 (bf16 store), 32 (GELU, fp32 store, split
-      // partials), 48 (DGELU), 64 (residual / accumulate).  An op issued after the awaited DMA
-      // stays outstanding while it does (in-order completion), so 8 + S is the loosest exact wait.
+      // vmcnt counts of the first step after an epilogue that issued fst vector-memory ops: 8 + fst
+      // (Epi::vmem_ops has the derivation and the values)
 #define WAITV(N) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(N) : "memory")
 #define WAITF() do { if (fst >= 55) WAITV(63); else if (fst == 48) WAITV(56); else if (fst == 32) WAITV(40); \
                      else if (fst == 16) WAITV(24); else WAITV(8); } while (0)
@@ -988,8 +1065,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
                        :: "v"(acc[mi][ni]), "v"(vo), "s"(rw), "s"(mi * rs16), "i"(ni * 64) : "memory");
       }
     } else
-    if ((EPI != EPI_PARTIAL || g.kz <= 1) && tile >= g.t_full) {
-      // K-range of a tail tile: raw fp32 partial into its [256][256] slab
+    if (RAW_TAIL()) {
+      // raw fp32 partial into its [256][256] slab
       const __amdgpu_buffer_rsrc_t rw = make_rsrc(g.tail_ws + (int64_t)(tile - g.t_full) * BM * BN, BM * BN * 4);
       const uint32_t wbase = (uint32_t)(((wm * 128 + lr) * BN + wn * 64 + lc4) * 4);
 #pragma unroll
@@ -1006,22 +1083,21 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
     // serialising the epilogue.  C never aliases A/B here (host contract).  The range
     // check drops rows >= M; the row offset is a scalar per mi, the column an immediate.
     {
-      constexpr int CES = sizeof(TC) == 2 && EPI != EPI_PARTIAL && EB != VITMI_EPI_ACCUM &&
-                                  EB != VITMI_EPI_RESIDUAL ? 2 : 4;
+      constexpr int EB = E::base, CES = E::template ces<TC>;
       int64_t zoff = 0;
-      if constexpr (EPI == EPI_PARTIAL) zoff = (int64_t)(blockIdx.z + zs) * g.split_stride;
+      if constexpr (E::partial) zoff = (int64_t)(blockIdx.z + zs) * g.split_stride;
       char* cbase = (char*)g.C + (zoff + m0 * g.ldc + n0) * CES;
       const __amdgpu_buffer_rsrc_t rc = make_rsrc(cbase, clamp_bytes(((g.M - m0) * g.ldc - n0) * CES));
-      // EPI_GELU_X3: the second hi copy at column N + c, lo at 2N + c
+      // SPLIT_X3: the second hi copy at column N + c, lo at 2N + c
       [[maybe_unused]] __amdgpu_buffer_rsrc_t rc2 = rc, rc3 = rc;
-      if constexpr (EPI == EPI_GELU_X3) {
+      if constexpr (E::split == SPLIT_X3) {
         rc2 = make_rsrc(cbase + g.N * 2, clamp_bytes(((g.M - m0) * g.ldc - n0 - g.N) * 2));
         rc3 = make_rsrc(cbase + g.N * 4, clamp_bytes(((g.M - m0) * g.ldc - n0 - 2 * g.N) * 2));
       }
-      // EPI_GELU_F8: the e4m3 part from byte 2N of the 4N-byte row, 64-column blocks [hi8 | lo8]
+      // SPLIT_F8: the e4m3 part from byte 2N of the 4N-byte row, 64-column blocks [hi8 | lo8]
       // (common.h f8_off): a wave's 64 columns are one block, 128 B per row at 2 n0 + 128 wn --
       // the same byte offsets as its bf16 hi, so `flush` writes it unchanged from its own base
-      if constexpr (EPI == EPI_GELU_F8)
+      if constexpr (E::split == SPLIT_F8)
         rc2 = make_rsrc((char*)g.C + m0 * g.ldc * 2 + 2 * g.N + n0 * 2,
                         clamp_bytes((g.M - m0) * g.ldc * 2 - 2 * g.N - n0 * 2));
       const int rstride = (int)(16 * g.ldc * CES);     // bytes between mi row groups
@@ -1040,7 +1116,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
         colc[ni] = cok[ni] ? col : g.N - 4;
         vb[ni] = cok[ni] ? vbase : 0x80000000u;
         bv[ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (HAS_BIAS)
+        if constexpr (E::has_bias)
           bv[ni] = *(const f32x4*)(smem + 2 * STAGE + tpar * 1024 + (wn * 64 + ni * 16 + lc4) * 4);
       }
       [[maybe_unused]] __amdgpu_buffer_rsrc_t ru = rc;
@@ -1062,8 +1138,16 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
       // and another lane's read of it (no store-to-load forwarding or reordering across it; the
       // LDS executes one wave's accesses in order)
       auto lane_xchg = [] { asm volatile("" ::: "memory"); };
-      // the image of row group mi -> rows m0 + wm*128 + 16 mi + (0..15) of the buffer `r` (bf16, ld)
-      auto flush = [&](__amdgpu_buffer_rsrc_t r, int64_t ld, int mi, bool aux = false) {
+      // the image of row group mi -> rows m0 + wm*128 + 16 mi + (0..15) of the buffer `r` (bf16, ld);
+      // `aux` (a std::bool_constant): gelu' and not C, which only selects the stores' cache policy
+#define FLUSH_ST(POLICY)                                                                                       \
+  asm volatile(VMEM_SGPR_GUARD                                                                                 \
+               "buffer_store_dwordx4 %0, %2, %4, %5 offen" POLICY "\n\t"                                       \
+               "buffer_store_dwordx4 %1, %3, %4, %5 offen" POLICY "\n\ts_nop 1"                                \
+               :: "v"(__builtin_bit_cast(u32x4, d[0])), "v"(__builtin_bit_cast(u32x4, d[1])), "v"(vo[0]),     \
+                  "v"(vo[1]), "s"(r), "s"((int)(mi * 16 * ld * 2))                                             \
+               : "memory")
+      auto flush = [&](__amdgpu_buffer_rsrc_t r, int64_t ld, int mi, auto aux) {
         lane_xchg();
         bf16x8 d[2];
         uint32_t vo[2];
@@ -1072,25 +1156,13 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
           d[j] = *(const bf16x8*)(scr + (8 * j + rr) * EPI_PITCH + cc * 16);
           vo[j] = ccok ? (uint32_t)(((int64_t)(wm * 128 + 8 * j + rr) * ld + wn * 64 + cc * 8) * 2) : 0x80000000u;
         }
-        if (aux) {
-          asm volatile(VMEM_SGPR_GUARD
-                       "buffer_store_dwordx4 %0, %2, %4, %5 offen" VITMI_ST_AUX "\n\t"
-                       "buffer_store_dwordx4 %1, %3, %4, %5 offen" VITMI_ST_AUX "\n\ts_nop 1"
-                       :: "v"(__builtin_bit_cast(u32x4, d[0])), "v"(__builtin_bit_cast(u32x4, d[1])), "v"(vo[0]),
-                          "v"(vo[1]), "s"(r), "s"((int)(mi * 16 * ld * 2))
-                       : "memory");
-        } else {
-          asm volatile(VMEM_SGPR_GUARD
-                       "buffer_store_dwordx4 %0, %2, %4, %5 offen" VITMI_ST_C16 "\n\t"
-                       "buffer_store_dwordx4 %1, %3, %4, %5 offen" VITMI_ST_C16 "\n\ts_nop 1"
-                       :: "v"(__builtin_bit_cast(u32x4, d[0])), "v"(__builtin_bit_cast(u32x4, d[1])), "v"(vo[0]),
-                          "v"(vo[1]), "s"(r), "s"((int)(mi * 16 * ld * 2))
-                       : "memory");
-        }
+        if constexpr (decltype(aux)::value) FLUSH_ST(VITMI_ST_AUX);
+        else FLUSH_ST(VITMI_ST_C16);
         lane_xchg();   // and the next writes of the image stay after these reads
       };
-      [[maybe_unused]] bf16x4 lo3[4];   // EPI_GELU_X3: lo = bf16(a - hi) of the row group's fragments
-      [[maybe_unused]] uint32_t f8h[4], f8l[4];   // EPI_GELU_F8: hi8, lo8 (4 e4m3 each) of the fragments
+#undef FLUSH_ST
+      [[maybe_unused]] bf16x4 lo3[4];   // SPLIT_X3: lo = bf16(a - hi) of the row group's fragments
+      [[maybe_unused]] uint32_t f8h[4], f8l[4];   // SPLIT_F8: hi8, lo8 (4 e4m3 each) of the fragments
       // one output fragment (row group mi, column group ni); `ld` = the epilogue's loaded operand.
       // Returns the fragment of the second output (gelu') for BIAS_GELU.
       auto emit = [&](int mi, int ni, f32x4 ldv, bf16x4 ldb) -> bf16x4 {
@@ -1098,31 +1170,30 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
         f32x4 v = acc[mi][ni] + bv[ni];
         const int soff = mi * rstride;
         [[maybe_unused]] f32x4 df;   // dropout factors of the 4 columns
-        if constexpr (DROP) {
+        if constexpr (E::drop) {   // (written out here and in the residual epilogue below: see there)
           const uint32_t rk = drop_row_key(g.drop_seed, g.drop_site, (uint32_t)(m0 + wm * 128 + mi * 16 + lr));
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             df[e] = drop_hash(rk, (uint32_t)(colc[ni] + e)) >= g.drop_thresh ? g.drop_scale : 0.f;
         }
-        if constexpr (EPI == EPI_RESIDUAL_DROP) v = v * df + ldv;
-        if constexpr (EPI == VITMI_EPI_RESIDUAL || EPI == VITMI_EPI_ACCUM) v += ldv;
+        if constexpr (E::loads == LD_C) v += ldv;   // (the residual epilogues do not come through here)
         if constexpr (EB == VITMI_EPI_BIAS_GELU) {
           f32x4 a4, g4;                        // gelu(u), gelu'(u) (kept for DGELU)
           gelu4(v, a4, g4);
           v = a4;
-          if constexpr (DROP) {                // dropped: a = gelu(u) m/(1-p), aux = gelu'(u) m/(1-p)
+          if constexpr (E::drop) {             // dropped: a = gelu(u) m/(1-p), aux = gelu'(u) m/(1-p)
             v *= df;
             g4 *= df;
           }
 #pragma unroll
           for (int e = 0; e < 4; ++e) u[e] = (bf16)g4[e];
-        } else if constexpr (EPI == VITMI_EPI_DGELU) {
+        } else if constexpr (EB == VITMI_EPI_DGELU) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] *= (float)ldb[e];   // aux = gelu'(u) from the forward
           csum[ni] += v;                                       // rows >= M hold 0 (zero A rows)
         }
         if constexpr (CES == 4) {
-          if constexpr (EPI == EPI_PARTIAL) {
+          if constexpr (E::partial) {
             asm volatile(VMEM_SGPR_GUARD "buffer_store_dwordx4 %0, %1, %2, %3 offen offset:%4" VITMI_ST_PART "\n\ts_nop 1"
                          :: "v"(v), "v"(vb[ni]), "s"(rc), "s"(soff), "i"(ni * 64) : "memory");
           } else
@@ -1133,11 +1204,11 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] = (bf16)v[e];
           lds_put(ni, o);
-          if constexpr (EPI == EPI_GELU_X3) {
+          if constexpr (E::split == SPLIT_X3) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) lo3[ni][e] = (bf16)(v[e] - (float)o[e]);
           }
-          if constexpr (EPI == EPI_GELU_F8) {
+          if constexpr (E::split == SPLIT_F8) {
             bf16x4 h_;
             split_f8(v, h_, f8h[ni], f8l[ni]);
           }
@@ -1150,20 +1221,20 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) us[ni] = emit(mi, ni, ldv[ni], ldb[ni]);
         if constexpr (CES == 2) {
-          flush(rc, g.ldc, mi);
-          if constexpr (EPI == EPI_GELU_X3) {   // the same image again at +N, then lo at +2N
-            flush(rc2, g.ldc, mi);
+          flush(rc, g.ldc, mi, std::false_type{});
+          if constexpr (E::split == SPLIT_X3) {   // the same image again at +N, then lo at +2N
+            flush(rc2, g.ldc, mi, std::false_type{});
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) lds_put(ni, lo3[ni]);
-            flush(rc3, g.ldc, mi);
+            flush(rc3, g.ldc, mi, std::false_type{});
           }
-          if constexpr (EPI == EPI_GELU_F8) {   // the [hi8 | lo8] block image, 128 B per row
+          if constexpr (E::split == SPLIT_F8) {   // the [hi8 | lo8] block image, 128 B per row
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) {
               *(uint32_t*)(scr + lr * EPI_PITCH + ni * 16 + lc4) = f8h[ni];
               *(uint32_t*)(scr + lr * EPI_PITCH + 64 + ni * 16 + lc4) = f8l[ni];
             }
-            flush(rc2, g.ldc, mi);
+            flush(rc2, g.ldc, mi, std::false_type{});
           }
           if constexpr (EB == VITMI_EPI_BIAS_GELU) {
             if (g.aux_tiled) {   // straight from the registers: 2 KiB-wide stores (aux_at)
@@ -1179,17 +1250,17 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
             } else {
 #pragma unroll
               for (int ni = 0; ni < 4; ++ni) lds_put(ni, us[ni]);
-              flush(ru, g.ldaux, mi, true);
+              flush(ru, g.ldaux, mi, std::true_type{});
             }
           }
         }
       };
-      if constexpr (EB == VITMI_EPI_RESIDUAL || EPI == VITMI_EPI_ACCUM || EPI == VITMI_EPI_DGELU) {
+      if constexpr (E::loads != LD_NONE) {
         // epilogues that load: RB row groups at a time (all 4 column groups each; 64 VGPRs of
         // loaded operand per wait -- the fragment registers are free here), stored row by row
         // like the store-only epilogues below
-        constexpr int RB = EPI == VITMI_EPI_DGELU ? VITMI_EPI_RB_BF16 : VITMI_EPI_RB_F32;
-        if constexpr (EPI == VITMI_EPI_DGELU) {
+        constexpr int RB = E::loads == LD_AUX ? VITMI_EPI_RB_BF16 : VITMI_EPI_RB_F32;
+        if constexpr (E::loads == LD_AUX) {
           // gelu'(u) arrives as whole 128-B lines too: each lane loads 16 B of one row (8 rows x
           // 128 B per instruction; a C^T-layout load would take 16 rows x 32 B), the wave writes
           // the 16-row group to its LDS image and reads it back in the accumulator's layout.
@@ -1245,7 +1316,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
               emit_row(mi, z4, lb);
             }
           }
-        } else if constexpr (EB == VITMI_EPI_RESIDUAL) {
+        } else if constexpr (E::loads == LD_RESIDUAL) {
           // fp32 residual in, fp32 out, both as whole lines through the LDS image, half a row
           // group's columns (16 rows x 32 fp32 = one 128-B line per row) at a time: lane (rr8, c8)
           // moves 16 B of row 8j + rr8, then EVERY lane updates its two accumulator fragments of
@@ -1275,7 +1346,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
             for (int h = 0; h < RB; ++h) {
               const int mi = RB * mp + h;
               [[maybe_unused]] float pf = 1.f;   // the lane's row of this row group: its sample's factor
-              if constexpr (PATH) pf = path_factor(g, m0 + wm * 128 + mi * 16 + lr);
+              if constexpr (E::path) pf = path_factor(g, m0 + wm * 128 + mi * 16 + lr);
 #pragma unroll
               for (int pp = 0; pp < 2; ++pp) {
 #pragma unroll
@@ -1285,14 +1356,16 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
                 for (int q = 0; q < 2; ++q) {
                   const int ni = 2 * pp + q;
                   f32x4* pr = (f32x4*)(scr + lr * P32 + (q * 16 + lc4) * 4);
+                  // the branch value as `branch4` forms it, written out (with the sample factor
+                  // taken once per row group): through the helper these kernels spill more
                   f32x4 v = acc[mi][ni] + bv[ni];
-                  if constexpr (DROP) {
+                  if constexpr (E::drop) {
                     const uint32_t rk = drop_row_key(g.drop_seed, g.drop_site, (uint32_t)(m0 + wm * 128 + mi * 16 + lr));
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
                       v[e] *= drop_hash(rk, (uint32_t)(colc[ni] + e)) >= g.drop_thresh ? g.drop_scale : 0.f;
                   }
-                  if constexpr (PATH) v *= pf;
+                  if constexpr (E::path) v *= pf;
                   *pr = v + *pr;
                 }
                 lane_xchg();
@@ -1308,24 +1381,22 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
               }
             }
           }
-        } else
+        } else {   // LD_C: accumulate onto C, loaded in the accumulator's layout
+          const bf16x4 zb[4] = {};
 #pragma unroll
-        for (int mp = 0; mp < 8 / RB; ++mp) {
-          f32x4 ld4[RB][4];
-          bf16x4 ldu[RB][4];
+          for (int mp = 0; mp < 8 / RB; ++mp) {
+            f32x4 ld4[RB][4];
 #pragma unroll
-          for (int h = 0; h < RB; ++h) {
-            const int64_t row = min(m0 + wm * 128 + (RB * mp + h) * 16 + lr, g.M - 1);
+            for (int h = 0; h < RB; ++h) {
+              const int64_t row = min(m0 + wm * 128 + (RB * mp + h) * 16 + lr, g.M - 1);
 #pragma unroll
-            for (int ni = 0; ni < 4; ++ni) {
-              if constexpr (EB == VITMI_EPI_RESIDUAL) ld4[h][ni] = *(const f32x4*)(g.residual + row * g.ldr + colc[ni]);
-              if constexpr (EPI == VITMI_EPI_ACCUM) ld4[h][ni] = *(const f32x4*)((const float*)g.C + row * g.ldc + colc[ni]);
+              for (int ni = 0; ni < 4; ++ni) ld4[h][ni] = *(const f32x4*)((const float*)g.C + row * g.ldc + colc[ni]);
             }
-          }
 #pragma unroll
-          for (int h = 0; h < RB; ++h) emit_row(RB * mp + h, ld4[h], ldu[h]);
+            for (int h = 0; h < RB; ++h) emit_row(RB * mp + h, ld4[h], zb);
+          }
         }
-        if constexpr (EPI == VITMI_EPI_DGELU) {
+        if constexpr (E::loads == LD_AUX) {
           if (g.colsum) {
             // sum the wave's 128 rows: 8 row groups in registers (above), then the 16 lanes
             // of a column group (lane & 15 = row, one DPP row): four row_shr adds leave the sum
@@ -1370,19 +1441,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
     ++st_it;
 #endif
     tpar ^= 1;
-    // the epilogue just issued: 32 stores (store-only, split partials) or 64 ops
-    {
-      // bf16 outputs: 2 stores per row group (+2 for gelu'); fp32 outputs: 32 direct stores;
-      // + 16 aux loads for DGELU, + 32 loads for residual / accumulate.  (DGELU's 4 column-sum
-      // stores only make the waits below stricter.)
-      constexpr int CES2 = sizeof(TC) == 2 && EPI != EPI_PARTIAL && EB != VITMI_EPI_ACCUM &&
-                           EB != VITMI_EPI_RESIDUAL;
-      constexpr int EP = CES2 ? (EPI == EPI_GELU_X3 ? 64 : EPI == EPI_GELU_F8 ? 48
-                                 : EB == VITMI_EPI_BIAS_GELU || EPI == VITMI_EPI_DGELU ? 32 : 16)
-                              : (EB == VITMI_EPI_RESIDUAL || EPI == VITMI_EPI_ACCUM ? 64
-                                 : EPI == VITMI_EPI_DGELU ? 48 : 32);
-      ep_ops = ((EPI != EPI_PARTIAL || g.kz <= 1) && tile >= g.t_full) ? 32 : EP;
-    }
+    // what the epilogue just issued (a raw tail partial: its 32 stores)
+    constexpr int EP = E::template vmem_ops<TC>;
+    ep_ops = RAW_TAIL() ? 32 : EP;
     if (!has_next) break;
     it = itn; tile = next; m0 = m0n; n0 = n0n; ks0 = ks0n; nku = nkn; zs = zsn; ra = ran; rb = rbn;
     if constexpr (GRP) {
@@ -1395,7 +1456,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
   if (!wm) barrier();
 #undef RD_A
 #undef RD_B
-#undef G256_MMA
+#undef RAW_TAIL
 }
 
 // split-K reduction: dst[i] += sum_z ws[z][i]
@@ -1497,7 +1558,7 @@ __global__ void splitk_reduce_group_kernel(RedSegs rs, int splits) {
 
 // Finish the tail tiles of a split gemm256 launch: sum the nsplit fp32 partials of each
 // element and apply the epilogue (the elementwise epi_store of the 128x128 kernel).
-template <typename T, typename TC, int EPI>
+template <typename T, typename TC, typename E>
 __global__ __launch_bounds__(256) void gemm_tail_fixup_kernel(GemmArgs g, int ntail) {
   const int64_t groups = (int64_t)ntail * (256 * 256 / 4);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (int64_t)gridDim.x * blockDim.x) {
@@ -1524,13 +1585,12 @@ __global__ __launch_bounds__(256) void gemm_tail_fixup_kernel(GemmArgs g, int nt
     } else {
       for (int z = 0; z < g.nsplit; ++z) a += *(const f32x4*)(pw + (int64_t)z * 65536);
     }
-    if constexpr ((EPI == VITMI_EPI_STORE || EPI == VITMI_EPI_DGELU) && std::is_same<TC, bf16>::value &&
-                  std::is_same<T, bf16>::value) {
+    if constexpr (E::plain && !E::second_out && E::template ces<TC> == 2 && std::is_same<T, bf16>::value) {
       // the store-only and DGELU bf16 outputs leave as 8-B vectors (4 columns; N % 8 == 0 is a
       // gemm256 precondition, and 4 aligned columns are contiguous in the tile-native gelu' too),
       // element for element the arithmetic of epi_store
       f32x4 v = a;
-      if constexpr (EPI == VITMI_EPI_STORE) {
+      if constexpr (E::has_bias) {
         if (g.bias) v += *(const f32x4*)(g.bias + col);
       } else {
         const bf16x4 gp = *(const bf16x4*)((const bf16*)g.aux + aux_at(g, row, col));
@@ -1543,31 +1603,19 @@ __global__ __launch_bounds__(256) void gemm_tail_fixup_kernel(GemmArgs g, int nt
       *(bf16x4*)((bf16*)g.C + row * g.ldc + col) = o;
       continue;
     }
-    if constexpr (EPI == VITMI_EPI_RESIDUAL) {
-      // fp32 residual in and out as 16-B vectors ((residual + acc) + bias, as epi_store)
+    if constexpr (E::loads == LD_RESIDUAL && (E::path || !E::drop)) {
+      // fp32 residual in and out as 16-B vectors: (residual + acc) + bias as epi_store, or the
+      // scaled branch + residual (see `branch`; RESIDUAL_DROP alone goes element by element below)
       const f32x4 r = *(const f32x4*)(g.residual + row * g.ldr + col);
       const f32x4 bv = g.bias ? *(const f32x4*)(g.bias + col) : f32x4{0.f, 0.f, 0.f, 0.f};
-      *(f32x4*)((float*)g.C + row * g.ldc + col) = (r + a) + bv;
-      continue;
-    }
-    if constexpr (EpiOf<EPI>::path) {
-      // the same vectors with the branch scaled: residual + (acc + bias) [* element keep] * sample factor
-      const f32x4 r = *(const f32x4*)(g.residual + row * g.ldr + col);
-      f32x4 v = a + (g.bias ? *(const f32x4*)(g.bias + col) : f32x4{0.f, 0.f, 0.f, 0.f});
-      if constexpr (EpiOf<EPI>::drop) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] *= drop_factor(g, row, col + j);
-      }
-      *(f32x4*)((float*)g.C + row * g.ldc + col) = v * path_factor(g, row) + r;
+      if constexpr (E::path) *(f32x4*)((float*)g.C + row * g.ldc + col) = branch4<E>(g, a + bv, row, col) + r;
+      else *(f32x4*)((float*)g.C + row * g.ldc + col) = (r + a) + bv;
       continue;
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (col + j >= g.N) break;
-      constexpr int EB = EpiOf<EPI>::base;
-      const float bv = (g.bias && (EB == VITMI_EPI_STORE || EB == VITMI_EPI_BIAS_GELU || EB == VITMI_EPI_RESIDUAL))
-                           ? g.bias[col + j] : 0.f;
-      epi_store<T, TC, EPI>(g, row, col + j, a[j], bv);
+      epi_store<T, TC, E>(g, row, col + j, a[j], (g.bias && E::has_bias) ? g.bias[col + j] : 0.f);
     }
   }
 }
@@ -1678,26 +1726,20 @@ static size_t tail_ws_bytes(int64_t M, int64_t N, int64_t K) {
   const int nwg = (int)(((M + 255) / 256) * ((N + 255) / 256));
   int S, ks, ntail;
   if (nwg <= 0 || !tail_plan(nwg, grid256(nwg, 1), (int)((K + 63) / 64), S, ks, ntail)) return 0;
-  // (sized for any epilogue; launch_t may still decide not to split, see tail_ok)
+  // (sized for any epilogue; launch_t may still decide not to split, see Epi::tail_split)
   return (size_t)ntail * S * 256 * 256 * sizeof(float);
 }
 
-// Algorithmic work of one GEMM launch: 2MNK flops; bytes = A and B once, C written once
-// (read too for ACCUM: the += of a weight gradient), plus the epilogue's aux / residual.
-// Split-K partial slabs and tail partials are implementation traffic, not counted here.
-template <typename T, int EPI, typename TC>
+// Algorithmic work of one GEMM launch: 2MNK flops; bytes = A and B once plus the epilogue's side
+// (Epi::stat_bytes).  Split-K partial slabs and tail partials are implementation traffic, not
+// counted here.
+template <typename T, typename E, typename TC>
 static void gemm_stat(const void* kernel, const GemmArgs& g) {
-  constexpr int EB = EpiOf<EPI>::base;
   const double M = (double)g.M, N = (double)g.N, K = (double)g.K, es = sizeof(T);
-  double bytes = (M * K + N * K) * es;
-  if (EPI == EPI_PARTIAL || EB == VITMI_EPI_ACCUM) bytes += 2.0 * M * N * 4;   // dW += (read + write, fp32)
-  else bytes += M * N * sizeof(TC) * (EPI == EPI_GELU_X3 ? 3 : 1);
-  if (EB == VITMI_EPI_BIAS_GELU || EB == VITMI_EPI_DGELU) bytes += M * N * es;   // gelu' written / read
-  if (EB == VITMI_EPI_RESIDUAL) bytes += M * N * 4;                               // residual read
-  VITMI_STAT(kernel, 2.0 * M * N * K, bytes);
+  VITMI_STAT(kernel, 2.0 * M * N * K, (M * K + N * K) * es + E::template stat_bytes<TC>(M * N, es));
 }
 
-template <typename T, bool AK, bool BKM, int EPI, typename TC, bool F8 = false>
+template <typename T, bool AK, bool BKM, typename E, typename TC, bool F8 = false>
 static int launch_t(GemmArgs g, int splits, bool big, hipStream_t s) {
   if constexpr (sizeof(T) == 2) {
     if (big) {
@@ -1718,11 +1760,7 @@ static int launch_t(GemmArgs g, int splits, bool big, hipStream_t s) {
       g.t_full = nwg;
       g.nsplit = 1;
       g.ksplit = 0;
-      // measured: pays off for long reductions (>= 16 K-steps) and for the DGELU epilogue
-      // (whose partial units skip its aux loads); a wash or a loss for K = 768 otherwise
-      // (EPI_GELU_F8: the fix-up kernel does not write the split-f8 rows, so its tiles stay whole)
-      const bool tail_ok = (g.k_per_split / 64 >= VITMI_TAIL_MINK || EPI == VITMI_EPI_DGELU) && EPI != EPI_GELU_F8;
-      if (splits == 1 && tail_ok && EPI != EPI_PARTIAL && EPI != VITMI_EPI_ACCUM && g.tail_ws &&
+      if (splits == 1 && E::tail_split && g.k_per_split / 64 >= E::tail_min_ksteps(VITMI_TAIL_MINK) && g.tail_ws &&
           tail_plan(nwg, gx, (int)(g.k_per_split / 64), S, ks, ntail) &&
           g.tail_ws_bytes >= (size_t)ntail * S * 256 * 256 * sizeof(float)) {
         g.t_full = nwg - ntail;
@@ -1733,15 +1771,15 @@ static int launch_t(GemmArgs g, int splits, bool big, hipStream_t s) {
 #ifdef VITMI_GEMM_STAMPS
       g.stamps = g_stamps;
 #endif
-      hipLaunchKernelGGL((gemm256_kernel<AK, BKM, EPI, TC, F8>), dim3(gx, 1, splits), dim3(512), 0, s, g, units);
+      hipLaunchKernelGGL((gemm256_kernel<AK, BKM, E, TC, F8>), dim3(gx, 1, splits), dim3(512), 0, s, g, units);
       VITMI_LAUNCH_CHECK("gemm256_kernel");
-      gemm_stat<T, EPI, TC>((const void*)gemm256_kernel<AK, BKM, EPI, TC, F8>, g);
-      if constexpr (EPI != EPI_GELU_F8) if (units != nwg) {
+      gemm_stat<T, E, TC>((const void*)gemm256_kernel<AK, BKM, E, TC, F8>, g);
+      if constexpr (E::split != SPLIT_F8) if (units != nwg) {
         const int blocks = (ntail * 256 * 64 + 255) / 256;
-        hipLaunchKernelGGL((gemm_tail_fixup_kernel<T, TC, EPI>), dim3(blocks), dim3(256), 0, s, g, ntail);
+        hipLaunchKernelGGL((gemm_tail_fixup_kernel<T, TC, E>), dim3(blocks), dim3(256), 0, s, g, ntail);
         VITMI_LAUNCH_CHECK("gemm_tail_fixup_kernel");
         // partials read, outputs (+ gelu') written
-        VITMI_STAT((gemm_tail_fixup_kernel<T, TC, EPI>), 0, (double)ntail * 65536 * (4.0 * S + 2 * sizeof(TC)));
+        VITMI_STAT((gemm_tail_fixup_kernel<T, TC, E>), 0, (double)ntail * 65536 * (4.0 * S + 2 * sizeof(TC)));
         if (g.colsum) {   // the split tail tiles' column sums, from their finished output
           hipLaunchKernelGGL((tail_colsum_kernel<TC>), dim3(ntail * 2), dim3(256), 0, s, g);
           VITMI_LAUNCH_CHECK("tail_colsum_kernel");
@@ -1755,78 +1793,70 @@ static int launch_t(GemmArgs g, int splits, bool big, hipStream_t s) {
   g.tiles_n = (int)((g.N + BN - 1) / BN);
   const int tiles_m = (int)((g.M + BM - 1) / BM);
   dim3 grid(tiles_m * g.tiles_n, 1, splits);
-  hipLaunchKernelGGL((gemm_kernel<T, AK, BKM, EPI, TC, BM, BN, WM, WN>), grid, dim3(WM * WN * 64), 0, s, g);
+  hipLaunchKernelGGL((gemm_kernel<T, AK, BKM, E, TC, BM, BN, WM, WN>), grid, dim3(WM * WN * 64), 0, s, g);
   VITMI_LAUNCH_CHECK("gemm_kernel");
-  gemm_stat<T, EPI, TC>((const void*)gemm_kernel<T, AK, BKM, EPI, TC, BM, BN, WM, WN>, g);
+  gemm_stat<T, E, TC>((const void*)gemm_kernel<T, AK, BKM, E, TC, BM, BN, WM, WN>, g);
   return VITMI_OK;
 }
 
-template <typename T, int EPI, typename TC>
-static int launch_layout(int ak, int bk, GemmArgs g, int splits, bool big, hipStream_t s) {
-  if (ak && bk) return launch_t<T, true, true, EPI, TC>(g, splits, big, s);
-  if (ak && !bk) return launch_t<T, true, false, EPI, TC>(g, splits, big, s);
-  if (!ak && !bk) return launch_t<T, false, false, EPI, TC>(g, splits, big, s);
-  // A m-major x B k-major: weight gradients with the input operand stored transposed
-  if constexpr (EPI == EPI_PARTIAL || EPI == VITMI_EPI_ACCUM) return launch_t<T, false, true, EPI, TC>(g, splits, big, s);
-  return fail(VITMI_ERR_UNSUPPORTED, "gemm: layout A m-major x B k-major not instantiated");
+// ---- the dispatch table: every instantiation of the GEMM kernels (but the grouped one) ----
+// A x B layouts as a bit set (K: k-major, N: m/n-major)
+enum { L_KK = 1, L_KN = 2, L_NN = 4, L_NK = 8,
+       L_FWD = L_KK,                // forward linear layers only: x and W both k-major
+       L_3 = L_KK | L_KN | L_NN,    // every layout but A m-major x B k-major, which is for
+       L_ALL = L_3 | L_NK };        // weight gradients with the input operand stored transposed
+struct Key { int epi, lay; bool f8, bf16_c; };   // runtime epilogue code, one L_* bit, F8 operands, C type
+// One row: true if it answered k (rc: its result).  ON: whether the row exists for this operand type
+template <typename E, typename T, typename TC, int LAYS, bool F8 = false, bool ON = true>
+static bool row(const Key& k, const GemmArgs& g, int splits, bool big, hipStream_t s, int& rc) {
+  if constexpr (ON) {
+    if (k.epi != E::code || k.f8 != F8 || k.bf16_c != std::is_same<TC, bf16>::value) return false;
+    switch (k.lay & LAYS) {
+      case L_KK: if constexpr ((LAYS & L_KK) != 0) rc = launch_t<T, true, true, E, TC, F8>(g, splits, big, s); return true;
+      case L_KN: if constexpr ((LAYS & L_KN) != 0) rc = launch_t<T, true, false, E, TC, F8>(g, splits, big, s); return true;
+      case L_NN: if constexpr ((LAYS & L_NN) != 0) rc = launch_t<T, false, false, E, TC, F8>(g, splits, big, s); return true;
+      case L_NK: if constexpr ((LAYS & L_NK) != 0) rc = launch_t<T, false, true, E, TC, F8>(g, splits, big, s); return true;
+    }
+    if (LAYS != L_3) return false;   // (a forward-only epilogue elsewhere: refused as an unknown one below)
+    rc = fail(VITMI_ERR_UNSUPPORTED, "gemm: layout A m-major x B k-major not instantiated");
+    return true;
+  }
+  return false;
 }
-
+// The table, for operand type T.  (gemm_impl has checked c_dtype for the epilogues that write one
+// type only, so bf16_c is theirs.)
 template <typename T>
-static int dispatch(int ak, int bk, int c_dtype, int epi, GemmArgs g, int splits, bool big, hipStream_t s) {
-  const bool cbf = (c_dtype == VITMI_BF16);
-  switch (epi) {
-    case VITMI_EPI_STORE:
-      return cbf ? launch_layout<T, VITMI_EPI_STORE, bf16>(ak, bk, g, splits, big, s)
-                 : launch_layout<T, VITMI_EPI_STORE, float>(ak, bk, g, splits, big, s);
-    case VITMI_EPI_BIAS_GELU:
-      // bf16 operands: the GELU epilogue writes bf16 (activation and gelu'); gemm_impl rejects
-      // an fp32 C, so that variant is not instantiated
-      if constexpr (std::is_same<T, bf16>::value) return launch_layout<T, VITMI_EPI_BIAS_GELU, bf16>(ak, bk, g, splits, big, s);
-      else return cbf ? launch_layout<T, VITMI_EPI_BIAS_GELU, bf16>(ak, bk, g, splits, big, s)
-                      : launch_layout<T, VITMI_EPI_BIAS_GELU, float>(ak, bk, g, splits, big, s);
-    case VITMI_EPI_RESIDUAL:
-      return launch_layout<T, VITMI_EPI_RESIDUAL, float>(ak, bk, g, splits, big, s);
-    case VITMI_EPI_DGELU:
-      return cbf ? launch_layout<T, VITMI_EPI_DGELU, bf16>(ak, bk, g, splits, big, s)
-                 : launch_layout<T, VITMI_EPI_DGELU, float>(ak, bk, g, splits, big, s);
-    case VITMI_EPI_ACCUM:
-      return launch_layout<T, VITMI_EPI_ACCUM, float>(ak, bk, g, splits, big, s);
-    case EPI_PARTIAL:
-      return launch_layout<T, EPI_PARTIAL, float>(ak, bk, g, splits, big, s);
-    case EPI_GELU_DROP:   // forward linear layers only: x and W both k-major
-      if (!(ak && bk)) break;
-      if constexpr (std::is_same<T, bf16>::value) return launch_t<T, true, true, EPI_GELU_DROP, bf16>(g, splits, big, s);
-      else return cbf ? launch_t<T, true, true, EPI_GELU_DROP, bf16>(g, splits, big, s)
-                      : launch_t<T, true, true, EPI_GELU_DROP, float>(g, splits, big, s);
-    case EPI_RESIDUAL_DROP:
-      if (!(ak && bk)) break;
-      return launch_t<T, true, true, EPI_RESIDUAL_DROP, float>(g, splits, big, s);
-    case EPI_RESIDUAL_PATH:
-      if (!(ak && bk)) break;
-      return launch_t<T, true, true, EPI_RESIDUAL_PATH, float>(g, splits, big, s);
-    case EPI_RESIDUAL_DROP_PATH:
-      if (!(ak && bk)) break;
-      return launch_t<T, true, true, EPI_RESIDUAL_DROP_PATH, float>(g, splits, big, s);
-    case EPI_GELU_X3:   // forward linear layers, bf16 operands and output only (gemm_impl checks)
-      if (!(ak && bk)) break;
-      if constexpr (std::is_same<T, bf16>::value) return launch_t<T, true, true, EPI_GELU_X3, bf16>(g, splits, big, s);
-      break;
-  }
-  return fail(VITMI_ERR_INVALID, "gemm: unknown epilogue %d", epi);
-}
-
-// VITMI_BF16F8 operands (the forward linear layers of the bf16f8 knob): gemm256 only
-static int dispatch_f8(int c_dtype, int epi, GemmArgs g, hipStream_t s) {
-  switch (epi) {
-    case VITMI_EPI_STORE:
-      return c_dtype == VITMI_BF16 ? launch_t<bf16, true, true, VITMI_EPI_STORE, bf16, true>(g, 1, true, s)
-                                   : launch_t<bf16, true, true, VITMI_EPI_STORE, float, true>(g, 1, true, s);
-    case VITMI_EPI_RESIDUAL:
-      return launch_t<bf16, true, true, VITMI_EPI_RESIDUAL, float, true>(g, 1, true, s);
-    case EPI_GELU_F8:
-      return launch_t<bf16, true, true, EPI_GELU_F8, bf16, true>(g, 1, true, s);
-  }
-  return fail(VITMI_ERR_UNSUPPORTED, "gemm: VITMI_BF16F8 operands take STORE, RESIDUAL or BIAS_GELU|SPLIT_F8 (got %d)", epi);
+static int dispatch(const Key& k, const GemmArgs& g, int splits, bool big, hipStream_t s) {
+  constexpr bool B16 = std::is_same<T, bf16>::value;
+  int rc = VITMI_OK;
+  if (//  descriptor           ops C     layouts (F8 operands, row exists)
+      row<EpiStore,            T, bf16,  L_3>(k, g, splits, big, s, rc) ||
+      row<EpiStore,            T, float, L_3>(k, g, splits, big, s, rc) ||
+      // bf16 operands: the GELU epilogue writes bf16 (activation and gelu'); gemm_impl rejects an
+      // fp32 C, so that variant is not instantiated (the same for GELU with dropout)
+      row<EpiGelu,             T, bf16,  L_3>(k, g, splits, big, s, rc) ||
+      row<EpiGelu,             T, float, L_3, false, !B16>(k, g, splits, big, s, rc) ||
+      row<EpiResidual,         T, float, L_3>(k, g, splits, big, s, rc) ||
+      row<EpiDgelu,            T, bf16,  L_3>(k, g, splits, big, s, rc) ||
+      row<EpiDgelu,            T, float, L_3>(k, g, splits, big, s, rc) ||
+      row<EpiAccum,            T, float, L_ALL>(k, g, splits, big, s, rc) ||
+      row<EpiPartial,          T, float, L_ALL>(k, g, splits, big, s, rc) ||
+      row<EpiGeluDrop,         T, bf16,  L_FWD>(k, g, splits, big, s, rc) ||
+      row<EpiGeluDrop,         T, float, L_FWD, false, !B16>(k, g, splits, big, s, rc) ||
+      row<EpiResidualDrop,     T, float, L_FWD>(k, g, splits, big, s, rc) ||
+      row<EpiResidualPath,     T, float, L_FWD>(k, g, splits, big, s, rc) ||
+      row<EpiResidualDropPath, T, float, L_FWD>(k, g, splits, big, s, rc) ||
+      // bf16 operands and output only (gemm_impl checks)
+      row<EpiGeluX3,           T, bf16,  L_FWD, false, B16>(k, g, splits, big, s, rc) ||
+      // VITMI_BF16F8 operands (the forward linear layers of the bf16f8 knob): gemm256 only
+      row<EpiStore,            T, bf16,  L_FWD, true, B16>(k, g, splits, big, s, rc) ||
+      row<EpiStore,            T, float, L_FWD, true, B16>(k, g, splits, big, s, rc) ||
+      row<EpiResidual,         T, float, L_FWD, true, B16>(k, g, splits, big, s, rc) ||
+      row<EpiGeluF8,           T, bf16,  L_FWD, true, B16>(k, g, splits, big, s, rc))
+    return rc;
+  if (k.f8)
+    return fail(VITMI_ERR_UNSUPPORTED, "gemm: VITMI_BF16F8 operands take STORE, RESIDUAL or BIAS_GELU|SPLIT_F8 (got %d)", k.epi);
+  return fail(VITMI_ERR_INVALID, "gemm: unknown epilogue %d", k.epi);
 }
 
 static int bk_of(int dtype) { return dtype == VITMI_BF16 ? 64 : 32; }
@@ -1853,96 +1883,100 @@ static int choose_splits(int dtype, int64_t M, int64_t N, int64_t K, int reserve
   return (int)splits_for(tiles, ktiles, big ? avail : 2 * avail, cap);
 }
 
-static int gemm_impl(int dtype, int ak, int bk, int64_t M, int64_t N, int64_t K, const void* A,
-                     int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int c_dtype,
-                     int epi, const float* bias, void* aux, int64_t ldaux, const float* residual,
-                     int64_t ldr, void* ws, size_t ws_bytes, hipStream_t s, bool allow_split,
-                     const GemmArgs* drop = nullptr, float* colsum = nullptr, bool* colsum_done = nullptr) {
-  if (colsum_done) *colsum_done = false;
-  const bool aux_tiled = (epi & VITMI_EPI_AUX_TILED) != 0;
-  const bool x3 = (epi & VITMI_EPI_SPLIT_X3) != 0;
-  const bool sf8 = (epi & VITMI_EPI_SPLIT_F8) != 0;
-  epi &= ~(VITMI_EPI_AUX_TILED | VITMI_EPI_SPLIT_X3 | VITMI_EPI_SPLIT_F8);
+// One GEMM as the entry points ask for it: C[M,N] = epilogue(A B).  g is what the kernels will see:
+// a caller gives what every GEMM has positionally, GemmReq r{{A, B, C, M, N, K, lda, ldb, ldc}, dtype,
+// ak, bk, c_dtype, epi, ws, ws_bytes, stream}, and by name whatever else it uses (g.bias, g.aux /
+// ldaux, g.residual / ldr, g.drop, g.path and the last three fields); gemm_impl plans the rest of g.
+struct GemmReq {
+  GemmArgs g;
+  int dtype, ak, bk, c_dtype;  // VITMI_F32 / BF16 / BF16F8 / BF16F8W operands; A, B k-major?; C type
+  int epi;                     // runtime epilogue code | VITMI_EPI_AUX_TILED / SPLIT_X3 / SPLIT_F8
+  void* ws;
+  size_t ws_bytes;
+  hipStream_t s;
+  bool allow_split = false;    // (last positional one) an ACCUM may split K: weight gradients
+  float* colsum = nullptr;     // wanted: the fused column sums of a DGELU (GemmArgs::colsum);
+  bool* colsum_done = nullptr; // set if the launch wrote them
+};
+
+static int gemm_impl(GemmReq q) {
+  if (q.colsum_done) *q.colsum_done = false;
+  GemmArgs& g = q.g;
+  const int64_t M = g.M, N = g.N;
+  int64_t& K = g.K;     // (VITMI_BF16F8 operands: rewritten below, with dtype)
+  int& dtype = q.dtype;
+  const int ak = q.ak, bk = q.bk;
+  g.aux_tiled = (q.epi & VITMI_EPI_AUX_TILED) != 0;
+  const bool x3 = (q.epi & VITMI_EPI_SPLIT_X3) != 0;
+  const bool sf8 = (q.epi & VITMI_EPI_SPLIT_F8) != 0;
+  int epi = q.epi & ~(VITMI_EPI_AUX_TILED | VITMI_EPI_SPLIT_X3 | VITMI_EPI_SPLIT_F8);
   // VITMI_BF16F8: rows of 2K bf16 units ([hi | e4m3 parts]); the kernel sees bf16 operands over
   // K' = 2K with the e4m3 K-steps from K/64 on (GemmArgs::k8)
   // VITMI_BF16F8W (the weight-side correction alone): rows of 1.5K bf16 units [hi | one e4m3 byte per
   // k]; K' = 1.5K with the K/128 e4m3 K-steps (128 k each: hi8 of x against lo8 of w) from K/64 on
   const bool f8w = dtype == VITMI_BF16F8W;
   const bool f8 = dtype == VITMI_BF16F8 || f8w;
-  int64_t k8 = 0;
   if (f8) {
-    VITMI_CHECK_ARG(ak && bk && !allow_split, "gemm: VITMI_BF16F8 operands: forward linear layers (k-major A and B) only");
+    VITMI_CHECK_ARG(ak && bk && !q.allow_split, "gemm: VITMI_BF16F8 operands: forward linear layers (k-major A and B) only");
     VITMI_CHECK_ARG(K % (f8w ? 128 : 64) == 0 && N % 16 == 0, "gemm: VITMI_BF16F8%s needs K %% %d == 0 and N %% 16 == 0",
                     f8w ? "W" : "", f8w ? 128 : 64);
     const int64_t kr = f8w ? K + K / 2 : 2 * K;
-    VITMI_CHECK_ARG(lda >= kr && ldb >= kr, "gemm: VITMI_BF16F8 rows are 2K (VITMI_BF16F8W: 1.5K) bf16 units");
-    k8 = K / 64;
+    VITMI_CHECK_ARG(g.lda >= kr && g.ldb >= kr, "gemm: VITMI_BF16F8 rows are 2K (VITMI_BF16F8W: 1.5K) bf16 units");
+    g.k8 = (int)(K / 64);
     K = kr;
     dtype = VITMI_BF16;
   }
   if (sf8) {
-    VITMI_CHECK_ARG(f8 && epi == VITMI_EPI_BIAS_GELU && c_dtype == VITMI_BF16,
+    VITMI_CHECK_ARG(f8 && epi == VITMI_EPI_BIAS_GELU && q.c_dtype == VITMI_BF16,
                     "gemm: SPLIT_F8 needs BIAS_GELU, VITMI_BF16F8 operands and a bf16 output");
-    VITMI_CHECK_ARG(ldc >= 2 * N && N % 64 == 0, "gemm: SPLIT_F8 needs N %% 64 == 0 and ldc >= 2N (bf16 units)");
-    epi = EPI_GELU_F8;
+    VITMI_CHECK_ARG(g.ldc >= 2 * N && N % 64 == 0, "gemm: SPLIT_F8 needs N %% 64 == 0 and ldc >= 2N (bf16 units)");
+    epi = EpiGeluF8::code;
   }
   if (x3) {
-    VITMI_CHECK_ARG(epi == VITMI_EPI_BIAS_GELU && dtype == VITMI_BF16 && c_dtype == VITMI_BF16 && ak && bk,
+    VITMI_CHECK_ARG(epi == VITMI_EPI_BIAS_GELU && dtype == VITMI_BF16 && q.c_dtype == VITMI_BF16 && ak && bk,
                     "gemm: SPLIT_X3 needs BIAS_GELU, bf16 operands and output, k-major A and B");
-    VITMI_CHECK_ARG(ldc >= 3 * N, "gemm: SPLIT_X3 needs ldc >= 3N");
-    epi = EPI_GELU_X3;
+    VITMI_CHECK_ARG(g.ldc >= 3 * N, "gemm: SPLIT_X3 needs ldc >= 3N");
+    epi = EpiGeluX3::code;
   }
   VITMI_CHECK_ARG(dtype == VITMI_BF16 || dtype == VITMI_F32, "gemm: bad dtype %d", dtype);
   VITMI_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "gemm: negative size");
   if (M == 0 || N == 0) return VITMI_OK;
-  VITMI_CHECK_ARG(A && B && C, "gemm: null operand");
+  VITMI_CHECK_ARG(g.A && g.B && g.C, "gemm: null operand");
   const int BK = bk_of(dtype);
   if (ak) VITMI_CHECK_ARG(K % BK == 0, "gemm: k-major A needs K %% %d == 0 (K=%lld)", BK, (long long)K);
   if (bk) VITMI_CHECK_ARG(K % BK == 0, "gemm: k-major B needs K %% %d == 0 (K=%lld)", BK, (long long)K);
   const int es = dtype == VITMI_BF16 ? 2 : 4;
-  VITMI_CHECK_ARG((lda * es) % 16 == 0 && (ldb * es) % 16 == 0, "gemm: lda/ldb must be 16-byte multiples");
-  VITMI_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, "gemm: A/B must be 16-byte aligned");
-  VITMI_CHECK_ARG(ak ? lda >= K : lda >= M, "gemm: lda too small");
-  VITMI_CHECK_ARG(bk ? ldb >= K : ldb >= N, "gemm: ldb too small");
-  VITMI_CHECK_ARG(ldc >= N, "gemm: ldc too small");
+  VITMI_CHECK_ARG((g.lda * es) % 16 == 0 && (g.ldb * es) % 16 == 0, "gemm: lda/ldb must be 16-byte multiples");
+  VITMI_CHECK_ARG(((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.B % 16) == 0, "gemm: A/B must be 16-byte aligned");
+  VITMI_CHECK_ARG(ak ? g.lda >= K : g.lda >= M, "gemm: lda too small");
+  VITMI_CHECK_ARG(bk ? g.ldb >= K : g.ldb >= N, "gemm: ldb too small");
+  VITMI_CHECK_ARG(g.ldc >= N, "gemm: ldc too small");
   const int eb = epi_base(epi);
   if (eb == VITMI_EPI_BIAS_GELU || eb == VITMI_EPI_DGELU)
-    VITMI_CHECK_ARG(aux != nullptr && ldaux >= N, "gemm: epilogue needs aux");
-  if (aux_tiled) {
+    VITMI_CHECK_ARG(g.aux != nullptr && g.ldaux >= N, "gemm: epilogue needs aux");
+  if (g.aux_tiled) {
     VITMI_CHECK_ARG(eb == VITMI_EPI_BIAS_GELU || eb == VITMI_EPI_DGELU, "gemm: AUX_TILED needs BIAS_GELU or DGELU");
     VITMI_CHECK_ARG(dtype == VITMI_BF16, "gemm: AUX_TILED needs bf16 operands (a bf16 gelu')");
-    VITMI_CHECK_ARG(((uintptr_t)aux % 16) == 0, "gemm: AUX_TILED aux must be 16-byte aligned");
+    VITMI_CHECK_ARG(((uintptr_t)g.aux % 16) == 0, "gemm: AUX_TILED aux must be 16-byte aligned");
   }
-  if (eb == VITMI_EPI_RESIDUAL) VITMI_CHECK_ARG(residual != nullptr && ldr >= N, "gemm: residual missing");
+  if (eb == VITMI_EPI_RESIDUAL) VITMI_CHECK_ARG(g.residual != nullptr && g.ldr >= N, "gemm: residual missing");
   if (eb == VITMI_EPI_RESIDUAL || eb == VITMI_EPI_ACCUM)
-    VITMI_CHECK_ARG(c_dtype == VITMI_F32, "gemm: residual/accum epilogues write fp32");
+    VITMI_CHECK_ARG(q.c_dtype == VITMI_F32, "gemm: residual/accum epilogues write fp32");
   if (eb == VITMI_EPI_BIAS_GELU && dtype == VITMI_BF16)
-    VITMI_CHECK_ARG(c_dtype == VITMI_BF16, "gemm: the bias+GELU epilogue on bf16 operands writes bf16");
+    VITMI_CHECK_ARG(q.c_dtype == VITMI_BF16, "gemm: the bias+GELU epilogue on bf16 operands writes bf16");
   // 32-bit buffer offsets: one block's panel must stay under 2 GiB
-  VITMI_CHECK_ARG((ak ? 128 * lda : K * lda) * es < 0x7fffffffLL, "gemm: A panel exceeds 2 GiB");
+  VITMI_CHECK_ARG((ak ? 128 * g.lda : K * g.lda) * es < 0x7fffffffLL, "gemm: A panel exceeds 2 GiB");
 
-  const bool big = f8 || use256(dtype, M, N, K, allow_split && epi == VITMI_EPI_ACCUM);
+  const bool big = f8 || use256(dtype, M, N, K, q.allow_split && epi == VITMI_EPI_ACCUM);
   if (big) {
     init_cus();
-    VITMI_CHECK_ARG(ldc % 8 == 0 && (ldr % 4) == 0 && (ldaux % 8) == 0 && ((uintptr_t)C % 16) == 0,
+    VITMI_CHECK_ARG(g.ldc % 8 == 0 && (g.ldr % 4) == 0 && (g.ldaux % 8) == 0 && ((uintptr_t)g.C % 16) == 0,
                     "gemm: 16-byte aligned C/aux/residual rows required");
-    VITMI_CHECK_ARG(bias == nullptr || ((uintptr_t)bias % 16) == 0, "gemm: bias must be 16-byte aligned");
-    VITMI_CHECK_ARG((ak ? 256 * lda : K * lda) * 2 < 0x7fffffffLL, "gemm: A panel exceeds 2 GiB");
-  }
-  GemmArgs g{};
-  g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K;
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.bias = bias; g.aux = aux; g.ldaux = ldaux;
-  g.residual = residual; g.ldr = ldr;
-  g.aux_tiled = aux_tiled;
-  g.k8 = (int)k8;
-  if (drop) {
-    g.drop_seed = drop->drop_seed; g.drop_site = drop->drop_site;
-    g.drop_thresh = drop->drop_thresh; g.drop_scale = drop->drop_scale;
-    g.path_site = drop->path_site; g.path_thresh = drop->path_thresh; g.path_scale = drop->path_scale;
-    g.path_S = drop->path_S; g.path_magic = drop->path_magic;
+    VITMI_CHECK_ARG(g.bias == nullptr || ((uintptr_t)g.bias % 16) == 0, "gemm: bias must be 16-byte aligned");
+    VITMI_CHECK_ARG((ak ? 256 * g.lda : K * g.lda) * 2 < 0x7fffffffLL, "gemm: A panel exceeds 2 GiB");
   }
   int splits = 1;
-  if (allow_split && epi == VITMI_EPI_ACCUM) splits = choose_splits(dtype, M, N, K, g_reserved.load(std::memory_order_relaxed));
+  if (q.allow_split && epi == VITMI_EPI_ACCUM) splits = choose_splits(dtype, M, N, K, g_reserved.load(std::memory_order_relaxed));
   const int64_t ktiles = (K + BK - 1) / BK;
   g.k_per_split = ((ktiles + splits - 1) / splits) * BK;
   if (K == 0) g.k_per_split = BK;
@@ -1950,10 +1984,10 @@ static int gemm_impl(int dtype, int ak, int bk, int64_t M, int64_t N, int64_t K,
   if (splits < 1) splits = 1;
   if (splits > 1) {
     const size_t need = (size_t)splits * M * N * sizeof(float);
-    if (ws == nullptr || ws_bytes < need) splits = 1, g.k_per_split = ktiles * BK;
+    if (q.ws == nullptr || q.ws_bytes < need) splits = 1, g.k_per_split = ktiles * BK;
   }
-  bool big2 = big;
-  if (big2) {
+  bool big_ok = big;
+  if (big_ok) {
     // gemm256 keeps two K-steps in flight: every split must span >= 2 k-tiles
     const int64_t kps = g.k_per_split / BK;
     const int64_t last = ktiles - (int64_t)(splits - 1) * kps;
@@ -1964,37 +1998,34 @@ static int gemm_impl(int dtype, int ak, int bk, int64_t M, int64_t N, int64_t K,
         g.k_per_split = k2 * BK;
         splits = (int)((ktiles + k2 - 1) / k2);
       } else {
-        big2 = false;
+        big_ok = false;
       }
     }
   }
-  const bool big_ok = big2;
+  auto run = [&](int code, int c_dtype, const GemmArgs& ga, int nsplits) {
+    const Key k{code, ak ? (bk ? L_KK : L_KN) : (bk ? L_NK : L_NN), f8, c_dtype == VITMI_BF16};
+    return dtype == VITMI_BF16 ? dispatch<bf16>(k, ga, nsplits, big_ok, q.s) : dispatch<float>(k, ga, nsplits, big_ok, q.s);
+  };
   if (splits == 1) {
     g.k_per_split = (K > 0 ? ktiles : 1) * BK;
-    g.tail_ws = (float*)ws;   // tail split of the persistent gemm256 launch (if it fits)
-    g.tail_ws_bytes = ws ? ws_bytes : 0;
-    if (colsum && big_ok && dtype == VITMI_BF16 && epi == VITMI_EPI_DGELU) {
-      g.colsum = colsum;      // fused column sums (gemm256 DGELU epilogue only)
-      if (colsum_done) *colsum_done = true;
+    g.tail_ws = (float*)q.ws;   // tail split of the persistent gemm256 launch (if it fits)
+    g.tail_ws_bytes = q.ws ? q.ws_bytes : 0;
+    if (q.colsum && big_ok && dtype == VITMI_BF16 && epi == VITMI_EPI_DGELU) {
+      g.colsum = q.colsum;      // fused column sums (gemm256 DGELU epilogue only)
+      if (q.colsum_done) *q.colsum_done = true;
     }
-    if (f8) {
-      VITMI_CHECK_ARG(big_ok, "gemm: VITMI_BF16F8 needs >= 2 K-steps");
-      return dispatch_f8(c_dtype, epi, g, s);
-    }
-    if (dtype == VITMI_BF16) return dispatch<bf16>(ak, bk, c_dtype, epi, g, 1, big_ok, s);
-    return dispatch<float>(ak, bk, c_dtype, epi, g, 1, big_ok, s);
+    if (f8) VITMI_CHECK_ARG(big_ok, "gemm: VITMI_BF16F8 needs >= 2 K-steps");
+    return run(epi, q.c_dtype, g, 1);
   }
   // split-K: partial slabs then one reduction pass into C (+=)
   GemmArgs gp = g;
-  gp.C = ws; gp.ldc = N; gp.split_stride = M * N;
-  int rc = dtype == VITMI_BF16 ? dispatch<bf16>(ak, bk, VITMI_F32, EPI_PARTIAL, gp, splits, big_ok, s)
-                               : dispatch<float>(ak, bk, VITMI_F32, EPI_PARTIAL, gp, splits, big_ok, s);
-  if (rc) return rc;
-  VITMI_CHECK_ARG(ldc == N, "gemm: split-K accumulate needs a dense C");
+  gp.C = q.ws; gp.ldc = N; gp.split_stride = M * N;
+  if (int rc = run(EpiPartial::code, VITMI_F32, gp, splits)) return rc;
+  VITMI_CHECK_ARG(g.ldc == N, "gemm: split-K accumulate needs a dense C");
   const int64_t n = M * N;
   if ((n + 3) / 4 <= SMALL_RED_MAX && splits >= 16) {
-    hipLaunchKernelGGL(splitk_reduce_small_kernel, dim3((unsigned)(((n + 3) / 4 + 63) / 64)), dim3(1024), 0, s,
-                       (const float*)ws, (float*)C, n, splits, M * N);
+    hipLaunchKernelGGL(splitk_reduce_small_kernel, dim3((unsigned)(((n + 3) / 4 + 63) / 64)), dim3(1024), 0, q.s,
+                       (const float*)q.ws, (float*)g.C, n, splits, M * N);
     VITMI_LAUNCH_CHECK("splitk_reduce_small_kernel");
     VITMI_STAT(splitk_reduce_small_kernel, 0, (double)n * 4 * (splits + 2));
     return VITMI_OK;
@@ -2002,8 +2033,8 @@ static int gemm_impl(int dtype, int ak, int bk, int64_t M, int64_t N, int64_t K,
   int blocks = (int)((n / 4 + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, (const float*)ws,
-                     (float*)C, n, splits, M * N);
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, q.s, (const float*)q.ws,
+                     (float*)g.C, n, splits, M * N);
   VITMI_LAUNCH_CHECK("splitk_reduce_kernel");
   VITMI_STAT(splitk_reduce_kernel, 0, (double)n * 4 * (splits + 2));
   return VITMI_OK;
@@ -2094,9 +2125,8 @@ static int wgrad_group_impl(int dtype, int n, int64_t M, const WgProb* pr, void*
   if (!grouped) {
     for (int q = 0; q < n; ++q) {
       const WgProb& w = pr[q];
-      if (int rc = gemm_impl(dtype, 0, 0, w.N, w.K, M, w.dy, w.lddy, w.x, w.ldx, w.dw, w.K, VITMI_F32,
-                             VITMI_EPI_ACCUM, nullptr, nullptr, 0, nullptr, 0, ws, ws_bytes, s, true))
-        return rc;
+      GemmReq r{{w.dy, w.x, w.dw, w.N, w.K, M, w.lddy, w.ldx, w.K}, dtype, 0, 0, VITMI_F32, VITMI_EPI_ACCUM, ws, ws_bytes, s, true};
+      if (int rc = gemm_impl(r)) return rc;
     }
     return VITMI_OK;
   }
@@ -2143,9 +2173,9 @@ static int wgrad_group_impl(int dtype, int n, int64_t M, const WgProb* pr, void*
                   "K-steps", S, g.kz_steps, (long long)ktiles);
   const int nwg = (int)(tiles * S);
   const int gx = grid256(nwg, 1);
-  hipLaunchKernelGGL((gemm256_kernel<false, false, EPI_PARTIAL, float, false, true>), dim3(gx), dim3(512), 0, s, g, nwg);
+  hipLaunchKernelGGL((gemm256_kernel<false, false, EpiPartial, float, false, true>), dim3(gx), dim3(512), 0, s, g, nwg);
   VITMI_LAUNCH_CHECK("gemm256_kernel (grouped wgrad)");
-  VITMI_STAT((gemm256_kernel<false, false, EPI_PARTIAL, float, false, true>), flops, bytes);
+  VITMI_STAT((gemm256_kernel<false, false, EpiPartial, float, false, true>), flops, bytes);
   int blocks = (int)((rs.g0[n] + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3(blocks), dim3(256), 0, s, rs, S);
@@ -2181,8 +2211,9 @@ extern "C" int vitmi_gemm(int dtype, int a_kmajor, int b_kmajor, int64_t M, int6
                           int64_t ldc, int c_dtype, int epilogue, const float* bias, void* aux,
                           int64_t ldaux, const float* residual, int64_t ldr, void* workspace,
                           size_t ws_bytes, vitmi_stream_t stream) {
-  return gemm_impl(dtype, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, C, ldc, c_dtype, epilogue,
-                   bias, aux, ldaux, residual, ldr, workspace, ws_bytes, (hipStream_t)stream, true);
+  GemmReq r{{A, B, C, M, N, K, lda, ldb, ldc}, dtype, a_kmajor, b_kmajor, c_dtype, epilogue, workspace, ws_bytes, (hipStream_t)stream, true};
+  r.g.bias = bias; r.g.aux = aux; r.g.ldaux = ldaux; r.g.residual = residual; r.g.ldr = ldr;
+  return gemm_impl(r);
 }
 
 extern "C" size_t vitmi_gemm_workspace_size(int dtype, int a_kmajor, int b_kmajor, int64_t M,
@@ -2213,8 +2244,9 @@ extern "C" int vitmi_linear_fwd(int dtype, int64_t M, int64_t N, int64_t K, cons
                   "linear_fwd: bad epilogue %d", epilogue);
   const int64_t ldy = (epilogue & VITMI_EPI_SPLIT_X3) ? 3 * N : (epilogue & VITMI_EPI_SPLIT_F8) ? 2 * N : N;
   const int64_t ldk = dtype == VITMI_BF16F8 ? 2 * K : dtype == VITMI_BF16F8W ? K + K / 2 : K;   // (bf16 units)
-  return gemm_impl(dtype, 1, 1, M, N, K, x, ldk, w, ldk, y, ldy, y_dtype, epilogue, bias, aux, N,
-                   residual, N, workspace, ws_bytes, (hipStream_t)stream, false);
+  GemmReq r{{x, w, y, M, N, K, ldk, ldk, ldy}, dtype, 1, 1, y_dtype, epilogue, workspace, ws_bytes, (hipStream_t)stream};
+  r.g.bias = bias; r.g.aux = aux; r.g.ldaux = N; r.g.residual = residual; r.g.ldr = N;
+  return gemm_impl(r);
 }
 
 extern "C" int vitmi_linear_fwd_dropout(int dtype, int64_t M, int64_t N, int64_t K, const void* x,
@@ -2226,11 +2258,11 @@ extern "C" int vitmi_linear_fwd_dropout(int dtype, int64_t M, int64_t N, int64_t
   const int eb = epilogue & ~VITMI_EPI_AUX_TILED;
   VITMI_CHECK_ARG(eb == VITMI_EPI_BIAS_GELU || eb == VITMI_EPI_RESIDUAL,
                   "linear_fwd_dropout: epilogue must be BIAS_GELU or RESIDUAL (got %d)", epilogue);
-  GemmArgs d{};
-  d.drop_seed = seed; d.drop_site = site; d.drop_thresh = thresh; d.drop_scale = scale;
-  const int epi = (eb == VITMI_EPI_BIAS_GELU ? EPI_GELU_DROP : EPI_RESIDUAL_DROP) | (epilogue & VITMI_EPI_AUX_TILED);
-  return gemm_impl(dtype, 1, 1, M, N, K, x, K, w, K, y, N, y_dtype, epi, bias, aux, N, residual, N,
-                   workspace, ws_bytes, (hipStream_t)stream, false, &d);
+  const int epi = (eb == VITMI_EPI_BIAS_GELU ? EpiGeluDrop::code : EpiResidualDrop::code) | (epilogue & VITMI_EPI_AUX_TILED);
+  GemmReq r{{x, w, y, M, N, K, K, K, N}, dtype, 1, 1, y_dtype, epi, workspace, ws_bytes, (hipStream_t)stream};
+  r.g.bias = bias; r.g.aux = aux; r.g.ldaux = N; r.g.residual = residual; r.g.ldr = N;
+  r.g.drop_seed = seed; r.g.drop_site = site; r.g.drop_thresh = thresh; r.g.drop_scale = scale;
+  return gemm_impl(r);
 }
 
 extern "C" int vitmi_linear_fwd_droppath(int dtype, int64_t M, int64_t N, int64_t K, const void* x,
@@ -2250,14 +2282,14 @@ extern "C" int vitmi_linear_fwd_droppath(int dtype, int64_t M, int64_t N, int64_
                   (long long)M, (long long)rows_per_sample);
   VITMI_CHECK_ARG(path_map_exact(M, rows_per_sample), "linear_fwd_droppath: M * rows_per_sample must be <= 2^32 "
                   "(the row -> sample mapping is exact only there)");
-  GemmArgs d{};
-  d.drop_seed = seed; d.drop_site = drop_site; d.drop_thresh = drop_thresh; d.drop_scale = drop_scale;
-  d.path_site = path_site; d.path_thresh = path_thresh; d.path_scale = path_scale;
-  d.path_S = (uint32_t)rows_per_sample; d.path_magic = path_magic((uint32_t)rows_per_sample);
   // drop_thresh 0 keeps every element: the path-only epilogue, no element hash
-  const int epi = drop_thresh ? EPI_RESIDUAL_DROP_PATH : EPI_RESIDUAL_PATH;
-  return gemm_impl(dtype, 1, 1, M, N, K, x, K, w, K, y, N, y_dtype, epi, bias, nullptr, N, residual, N,
-                   workspace, ws_bytes, (hipStream_t)stream, false, &d);
+  const int epi = drop_thresh ? EpiResidualDropPath::code : EpiResidualPath::code;
+  GemmReq r{{x, w, y, M, N, K, K, K, N}, dtype, 1, 1, y_dtype, epi, workspace, ws_bytes, (hipStream_t)stream};
+  r.g.bias = bias; r.g.ldaux = N; r.g.residual = residual; r.g.ldr = N;
+  r.g.drop_seed = seed; r.g.drop_site = drop_site; r.g.drop_thresh = drop_thresh; r.g.drop_scale = drop_scale;
+  r.g.path_site = path_site; r.g.path_thresh = path_thresh; r.g.path_scale = path_scale;
+  r.g.path_S = (uint32_t)rows_per_sample; r.g.path_magic = path_magic((uint32_t)rows_per_sample);
+  return gemm_impl(r);
 }
 
 extern "C" size_t vitmi_linear_dgrad_workspace_size(int dtype, int64_t M, int64_t N, int64_t K) {
@@ -2273,8 +2305,9 @@ extern "C" int vitmi_linear_dgrad(int dtype, int64_t M, int64_t N, int64_t K, co
                       (epilogue & ~VITMI_EPI_AUX_TILED) == VITMI_EPI_DGELU,
                   "linear_dgrad: bad epilogue %d", epilogue);
   // dx[M,K] = dy[M,N] . W[N,K]: reduction over N; A = dy (k-major), B = W as [N][K] (n-major)
-  return gemm_impl(dtype, 1, 0, M, K, N, dy, N, w, K, dx, K, dx_dtype, epilogue, nullptr,
-                   const_cast<void*>(aux), K, nullptr, 0, workspace, ws_bytes, (hipStream_t)stream, false);
+  GemmReq r{{dy, w, dx, M, K, N, N, K, K}, dtype, 1, 0, dx_dtype, epilogue, workspace, ws_bytes, (hipStream_t)stream};
+  r.g.aux = const_cast<void*>(aux); r.g.ldaux = K;
+  return gemm_impl(r);
 }
 
 // Column-sum partial rows of the fused DGELU epilogue (two per 256-row tile).
@@ -2300,9 +2333,9 @@ extern "C" int vitmi_linear_dgrad_bias(int dtype, int64_t M, int64_t N, int64_t 
   bool fused = false;
   // the partial rows live in the workspace; the tail split is off on this path, so the
   // GEMM itself needs no other workspace
-  int rc = gemm_impl(dtype, 1, 0, M, K, N, dy, N, w, K, dx, K, dx_dtype, epilogue, nullptr, const_cast<void*>(aux),
-                     K, nullptr, 0, nullptr, 0, s, false, nullptr, (float*)workspace, &fused);
-  if (rc) return rc;
+  GemmReq r{{dy, w, dx, M, K, N, N, K, K}, dtype, 1, 0, dx_dtype, epilogue, nullptr, 0, s};
+  r.g.aux = const_cast<void*>(aux); r.g.ldaux = K; r.colsum = (float*)workspace; r.colsum_done = &fused;
+  if (int rc = gemm_impl(r)) return rc;
   if (fused) return launch_colsum_finish(K, (int)colsum_rows(M), (const float*)workspace, db, s);
   // other paths (128x128 kernel, fp32): separate column-sum pass over dx
   return vitmi_bias_grad(dx_dtype, M, K, dx, K, db, workspace, ws_bytes, stream);
@@ -2318,8 +2351,8 @@ extern "C" int vitmi_linear_wgrad(int dtype, int64_t M, int64_t N, int64_t K, co
                                   const void* x, float* dw, void* workspace, size_t ws_bytes,
                                   vitmi_stream_t stream) {
   // dW[N,K] += sum_m dy[m][n] x[m][k]: A(n,m) = dy (m-major rows of n), B(m,k) = x (k contiguous)
-  return gemm_impl(dtype, 0, 0, N, K, M, dy, N, x, K, dw, K, VITMI_F32, VITMI_EPI_ACCUM, nullptr,
-                   nullptr, 0, nullptr, 0, workspace, ws_bytes, (hipStream_t)stream, true);
+  GemmReq r{{dy, x, dw, N, K, M, N, K, K}, dtype, 0, 0, VITMI_F32, VITMI_EPI_ACCUM, workspace, ws_bytes, (hipStream_t)stream, true};
+  return gemm_impl(r);
 }
 
 static int wg_probs(int n, const int64_t* N, const int64_t* K, const void* const* dy, const int64_t* lddy,
