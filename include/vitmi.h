@@ -352,6 +352,55 @@ int vitmi_droppath_apply(int64_t M, int64_t N, const float* x, int64_t ldx, void
                          uint32_t drop_thresh, float drop_scale, vitmi_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Patch dropout (timm's patch_drop_rate, FLIP, the MAE encoder's random masking): in training each
+ * sample keeps K of its np patch tokens and the class token; every block then runs on K + 1 tokens.
+ *
+ * Number kept: K = max(1, int(np * (1.0 - rate))) (timm's PatchDropout), computed by the caller and
+ * passed down as an integer; 1 <= K <= np <= 4096 in every call below.
+ * Keys: key(b, p) = vitmi_dropout_hash(seed, PATCH_SITE, row = b, col = p), PATCH_SITE = 0x20000000
+ * (disjoint from the dropout sites 3i..3i+2 and from the drop-path sites 0x40000000 + ...); seed is
+ * the forward's single drop seed.
+ * Which patches are kept: sample b keeps the K patches with the smallest (key, p) pairs, in
+ * lexicographic order (ties are broken by the smaller p).  Two index tensors describe the subset:
+ *   keep[b][0..K) (int32): the kept patch numbers in ASCENDING order;
+ *   slot[b][p]    (int32): the position j of patch p in keep[b], or -1 when dropped.
+ * Token tensor: [B, K + 1, D]; row 0 is cls + pos[0], row 1 + j is tok(b, keep[b][j]) +
+ * pos[1 + keep[b][j]].  Nothing is rescaled; everything downstream sees a model with N = K + 1.
+ * Backward: dcls and dpos[0] as in vitmi_tokens_assemble_bwd; dpos[1 + p] += sum_b dx[b][1 +
+ * slot[b][p]] over the samples that kept p, b in ascending order by one thread per (p, d), no
+ * atomics: bitwise reproducible.  dW, dbias of the patch projection come from the B*K kept rows.
+ * The gathered kernels treat an index outside [0, np) as "no patch": the forward writes a zero
+ * row, the backward adds nothing.
+ *
+ * vitmi_patch_keep: one block per sample builds keep [B][K] and slot [B][np] (np^2 compares per
+ * sample on keys held in LDS); a pure function of (seed, site, b), no host read. */
+int vitmi_patch_keep(int B, int np, int K, uint32_t seed, uint32_t site, int32_t* keep, int32_t* slot,
+                     vitmi_stream_t stream);
+/* vitmi_patch_im2col with row b*K + j reading patch keep[b][j]: patches [B*K][C*P*P] of dtype */
+int vitmi_patch_im2col_keep(int dtype, int B, int C, int S, int P, int K, const int32_t* keep,
+                            const float* img, void* patches, vitmi_stream_t stream);
+/* x[b][0] = cls + pos[0];  x[b][1+j] = tok[b*K+j] + pos[1 + keep[b][j]]   (cls/pos may be NULL) */
+int vitmi_tokens_assemble_keep(int B, int np, int K, int D, const float* tok, const float* cls,
+                               const float* pos, const int32_t* keep, float* x, vitmi_stream_t stream);
+/* backward of the gathered assemble: dtok [B*K][D] (f32, and/or a bf16 copy) = dx[:,1:];  dpos
+ * [np+1][D] and dcls += the sums above   (NULL pointers skip that output) */
+int vitmi_tokens_assemble_keep_bwd(int B, int np, int K, int D, const float* dx, float* dtok,
+                                   void* dtok_lp, float* dcls, float* dpos, const int32_t* slot,
+                                   vitmi_stream_t stream);
+/* vitmi_patch_embed_fwd / _bwd over the kept patches: the same composition from the gathered pieces
+ * (bit-identical to calling them), the patch GEMM and its gradients at M = B*K rows.
+ * patches: [B*K][C*P*P] of dtype; x and dx: fp32 [B][K+1][D]; dpos: [np+1][D]. */
+size_t vitmi_patch_embed_keep_fwd_workspace_size(int dtype, int B, int C, int S, int P, int D, int K);
+int vitmi_patch_embed_keep_fwd(int dtype, int B, int C, int S, int P, int D, int K, const int32_t* keep,
+                               const float* img, const void* w, const float* bias, const float* cls,
+                               const float* pos, void* patches, float* x, void* workspace, size_t ws_bytes,
+                               vitmi_stream_t stream);
+size_t vitmi_patch_embed_keep_bwd_workspace_size(int dtype, int B, int C, int S, int P, int D, int K);
+int vitmi_patch_embed_keep_bwd(int dtype, int B, int C, int S, int P, int D, int K, const int32_t* slot,
+                               const float* dx, const void* patches, float* dw, float* dbias, float* dcls,
+                               float* dpos, void* workspace, size_t ws_bytes, vitmi_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * CvT stages (the reference's actual SLS model, models/CvT(Par).py:66-72).
  *
  * ConvEmbed = layers.Conv2D(D, kernel=k, strides=s, padding='same') (:203-212) as a GEMM over

@@ -84,6 +84,72 @@ extern "C" int vitmi_patch_embed_bwd(int dtype, int B, int C, int S, int P, int 
   return VITMI_OK;
 }
 
+// ---- patch embedding of the kept patches only (patch dropout, csrc/patchdrop.hip): the same
+// composition over rows = B*keep_n gathered rows; the patch GEMM runs at M = B*keep_n
+namespace {
+int keep_geom(int B, int C, int S, int P, int D, int keep_n, PatchGeom& g) {
+  if (int rc = patch_geom(B, C, S, P, D, g)) return rc;
+  VITMI_CHECK_ARG(keep_n >= 1 && keep_n <= g.np && g.np <= 4096, "patch_embed_keep: need 1 <= K <= np <= 4096");
+  g.rows = (int64_t)B * keep_n;
+  return VITMI_OK;
+}
+}  // namespace
+
+extern "C" size_t vitmi_patch_embed_keep_fwd_workspace_size(int dtype, int B, int C, int S, int P, int D, int K) {
+  PatchGeom g;
+  if (keep_geom(B, C, S, P, D, K, g)) return 0;
+  return align_up((size_t)g.rows * D * sizeof(float)) + vitmi_linear_fwd_workspace_size(dtype, g.rows, D, g.K);
+}
+
+extern "C" int vitmi_patch_embed_keep_fwd(int dtype, int B, int C, int S, int P, int D, int K, const int32_t* keep,
+                                          const float* img, const void* w, const float* bias, const float* cls,
+                                          const float* pos, void* patches, float* x, void* workspace,
+                                          size_t ws_bytes, vitmi_stream_t stream) {
+  PatchGeom g;
+  if (int rc = keep_geom(B, C, S, P, D, K, g)) return rc;
+  VITMI_CHECK_ARG(keep && img && w && patches && x, "patch_embed_keep_fwd: null pointer");
+  const size_t need = vitmi_patch_embed_keep_fwd_workspace_size(dtype, B, C, S, P, D, K);
+  VITMI_CHECK_ARG(workspace && ws_bytes >= need, "patch_embed_keep_fwd: workspace %zu < %zu bytes", ws_bytes, need);
+  float* conv = (float*)workspace;
+  char* lin_ws = (char*)workspace + align_up((size_t)g.rows * D * sizeof(float));
+  if (int rc = vitmi_patch_im2col_keep(dtype, B, C, S, P, K, keep, img, patches, stream)) return rc;
+  if (int rc = vitmi_linear_fwd(dtype, g.rows, D, g.K, patches, w, bias, conv, VITMI_F32, VITMI_EPI_STORE, nullptr,
+                                nullptr, lin_ws, ws_bytes - (lin_ws - (char*)workspace), stream))
+    return rc;
+  return vitmi_tokens_assemble_keep(B, (int)g.np, K, D, conv, cls, pos, keep, x, stream);
+}
+
+extern "C" size_t vitmi_patch_embed_keep_bwd_workspace_size(int dtype, int B, int C, int S, int P, int D, int K) {
+  PatchGeom g;
+  if (keep_geom(B, C, S, P, D, K, g)) return 0;
+  const size_t wg = vitmi_linear_wgrad_workspace_size(dtype, g.rows, D, g.K);
+  const size_t bg = vitmi_bias_grad_workspace_size(g.rows, D);
+  return align_up((size_t)g.rows * D * es_of(dtype)) + (wg > bg ? wg : bg);
+}
+
+extern "C" int vitmi_patch_embed_keep_bwd(int dtype, int B, int C, int S, int P, int D, int K, const int32_t* slot,
+                                          const float* dx, const void* patches, float* dw, float* dbias,
+                                          float* dcls, float* dpos, void* workspace, size_t ws_bytes,
+                                          vitmi_stream_t stream) {
+  PatchGeom g;
+  if (int rc = keep_geom(B, C, S, P, D, K, g)) return rc;
+  VITMI_CHECK_ARG(slot && dx && patches, "patch_embed_keep_bwd: null pointer");
+  const size_t need = vitmi_patch_embed_keep_bwd_workspace_size(dtype, B, C, S, P, D, K);
+  VITMI_CHECK_ARG(workspace && ws_bytes >= need, "patch_embed_keep_bwd: workspace %zu < %zu bytes", ws_bytes, need);
+  void* dtok = workspace;
+  char* rest = (char*)workspace + align_up((size_t)g.rows * D * es_of(dtype));
+  const size_t rest_bytes = ws_bytes - (rest - (char*)workspace);
+  const bool lp = dtype == VITMI_BF16;
+  if (int rc = vitmi_tokens_assemble_keep_bwd(B, (int)g.np, K, D, dx, lp ? nullptr : (float*)dtok,
+                                              lp ? dtok : nullptr, dcls, dpos, slot, stream))
+    return rc;
+  if (dw)
+    if (int rc = vitmi_linear_wgrad(dtype, g.rows, D, g.K, dtok, patches, dw, rest, rest_bytes, stream)) return rc;
+  if (dbias)
+    if (int rc = vitmi_bias_grad(dtype, g.rows, D, dtok, D, dbias, rest, rest_bytes, stream)) return rc;
+  return VITMI_OK;
+}
+
 // ---- Dense backward: dx = dy W, dW += dy^T x, db += colsum(dy)  (autodiff of layers.Dense)
 extern "C" size_t vitmi_linear_bwd_workspace_size(int dtype, int64_t M, int64_t N, int64_t K) {
   size_t a = vitmi_linear_dgrad_workspace_size(dtype, M, N, K);

@@ -22,4 +22,7 @@ def __getattr__(name):
     if name == "DropPath":   # the stochastic-depth module (vitmi.modules), same lazy import
         from .modules import DropPath
         return DropPath
+    if name in ("patch_keep", "PATCH_SITE"):   # patch dropout's subset selection (vitmi.ops) and its hash site
+        from . import ops
+        return getattr(ops, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -118,6 +118,14 @@ SIGNATURES = {
     "vitmi_patch_embed_fwd": (I, [I, I, I, I, I, I, P, P, P, P, P, P, P, P, S, P]),
     "vitmi_patch_embed_bwd_workspace_size": (S, [I, I, I, I, I, I]),
     "vitmi_patch_embed_bwd": (I, [I, I, I, I, I, I, P, P, P, P, P, P, P, S, P]),
+    "vitmi_patch_keep": (I, [I, I, I, U, U, P, P, P]),
+    "vitmi_patch_im2col_keep": (I, [I, I, I, I, I, I, P, P, P, P]),
+    "vitmi_tokens_assemble_keep": (I, [I, I, I, I, P, P, P, P, P, P]),
+    "vitmi_tokens_assemble_keep_bwd": (I, [I, I, I, I, P, P, P, P, P, P, P]),
+    "vitmi_patch_embed_keep_fwd_workspace_size": (S, [I, I, I, I, I, I, I]),
+    "vitmi_patch_embed_keep_fwd": (I, [I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, S, P]),
+    "vitmi_patch_embed_keep_bwd_workspace_size": (S, [I, I, I, I, I, I, I]),
+    "vitmi_patch_embed_keep_bwd": (I, [I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, S, P]),
     "vitmi_linear_bwd_workspace_size": (S, [I, L, L, L]),
     "vitmi_linear_bwd": (I, [I, L, L, L, P, P, P, P, I, P, P, P, S, P]),
     "vitmi_xent_fwd": (I, [I, I, P, P, P, P]),

@@ -64,10 +64,16 @@ class ViTConfig:
     # dropped with probability linspace(0, drop_path_rate, depth)[i] and the kept ones scaled by
     # 1/(1-p) (DeiT: 0.1 for ViT-B).  0 = off.
     drop_path_rate: float = 0.0
+    # patch dropout (timm's patch_drop_rate, FLIP, the MAE encoder's random masking): in training
+    # each sample keeps a hashed subset of ``kept_patches`` of its patch tokens (the class token
+    # always) and every block runs on the shortened sequence; nothing is rescaled.  0 = off.
+    patch_drop_rate: float = 0.0
 
     def __post_init__(self):
         if not 0.0 <= self.drop_path_rate < 1.0:   # (also refuses NaN)
             raise ValueError(f"drop_path_rate must be in [0, 1) (got {self.drop_path_rate})")
+        if not 0.0 <= self.patch_drop_rate < 1.0:
+            raise ValueError(f"patch_drop_rate must be in [0, 1) (got {self.patch_drop_rate})")
 
     def drop_path_rates(self) -> list:
         """Per-block drop-path rate: linspace(0, drop_path_rate, depth), block 0 = 0 (MS_CvT, timm)."""
@@ -85,6 +91,11 @@ class ViTConfig:
     @property
     def seq_len(self) -> int:
         return self.num_patches + (1 if self.with_cls_token else 0)
+
+    @property
+    def kept_patches(self) -> int:
+        """K of patch dropout: max(1, int(num_patches * (1 - patch_drop_rate))), timm's PatchDropout."""
+        return max(1, int(self.num_patches * (1.0 - self.patch_drop_rate)))
 
     @property
     def head_dim(self) -> int:
@@ -105,16 +116,20 @@ class ViTConfig:
     def replace(self, **kw) -> "ViTConfig":
         return dataclasses.replace(self, **kw)
 
-    def flops_per_image_fwd(self) -> float:
+    def flops_per_image_fwd(self, kept_patches: "int | None" = None) -> float:
         """Algorithmic forward FLOPs per image (2 x MAC over every dense contraction).
 
         Counts patch-embed, QKV, QK^T, PV, out-proj, fc1, fc2 and head, as
         BASELINE.md prescribes (LN/softmax/GELU excluded).  Mirrors the MAC
         convention of ``Attention.compute_macs`` (``old_codes/MS_CvT.py:214-286``).
+        ``kept_patches``: count a patch-dropped training forward, which embeds that many
+        patches and runs the blocks on them plus the class token (None: the full sequence).
         """
-        D, N, F, L = self.embed_dim, self.seq_len, self.mlp_dim, self.depth
+        D, F, L = self.embed_dim, self.mlp_dim, self.depth
+        npk = self.num_patches if kept_patches is None else int(kept_patches)
+        N = npk + (1 if self.with_cls_token else 0)
         P2C = self.patch_size * self.patch_size * self.in_chans
-        macs = self.num_patches * P2C * D
+        macs = npk * P2C * D
         per_block = N * D * 3 * D + 2 * N * N * D + N * D * D + 2 * N * D * F
         macs += L * per_block + D * self.num_classes
         return 2.0 * macs

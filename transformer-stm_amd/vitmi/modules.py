@@ -683,21 +683,27 @@ class ConvEmbed(nn.Module):
         _check_cuda(x)
         B, C, S, _ = x.shape
         G = S // self.patch_size
-        tok = _EmbedFn.apply(x, self, None, None, *self.parameters())  # [B, 1+np, D] w/o cls
+        tok = _EmbedFn.apply(x, self, None, None, None, *self.parameters())  # [B, 1+np, D] w/o cls
         return tok[:, 1:].transpose(1, 2).reshape(B, -1, G, G)
 
 
 class _EmbedFn(torch.autograd.Function):
-    """im2col -> patch GEMM (+bias) [-> LN] -> cls concat + pos-embed, one token tensor."""
+    """im2col -> patch GEMM (+bias) [-> LN] -> cls concat + pos-embed, one token tensor.  ``keep``:
+    the (keep, slot) index pair of patch dropout (ops.patch_keep) -> only the kept patches are
+    embedded, [B, K+1, D]; None -> every patch."""
 
     @staticmethod
-    def forward(ctx, img, emb, cls, pos, *params):
+    def forward(ctx, img, emb, cls, pos, keep, *params):
         T = ops.torch_dtype(emb.dtype)
         B, C, S, _ = img.shape
         P = emb.patch_size
         G = S // P
         np_ = G * G
         D = emb.proj.weight.shape[0]
+        if keep is not None and emb.dtype in ("bf16x3", "bf16f8"):
+            raise ValueError(f"vitmi: dtype '{emb.dtype}' is the parity / evaluation knob; patch dropout is not "
+                             "supported")
+        kp = keep[0] if keep is not None else None
         w = _lp(emb, emb.proj.weight, T).reshape(D, -1)
         cls_ = cls.detach().reshape(-1) if cls is not None else None
         pos_ = pos.detach().reshape(-1) if pos is not None else None
@@ -715,25 +721,32 @@ class _EmbedFn(torch.autograd.Function):
             saved = [patches]
         elif emb.norm is None:
             # the §8(b) entry point: im2col -> patch GEMM (+bias) -> cls concat + pos-embed
-            x, patches = ops.patch_embed_fwd(img.contiguous().float(), w, emb.proj.bias, cls_, pos_, P, T)
+            if kp is None:
+                x, patches = ops.patch_embed_fwd(img.contiguous().float(), w, emb.proj.bias, cls_, pos_, P, T)
+            else:
+                x, patches = ops.patch_embed_keep_fwd(img.contiguous().float(), w, emb.proj.bias, cls_, pos_, P, kp, T)
             saved = [patches]
         else:
-            patches = ops.patch_im2col(img.contiguous().float(), P, T)
+            imgf = img.contiguous().float()
+            patches = ops.patch_im2col(imgf, P, T) if kp is None else ops.patch_im2col_keep(imgf, P, kp, T)
             conv = ops.linear_fwd(patches, w, emb.proj.bias, F32)
             y, mean, rstd = ops.layernorm_fwd(conv, emb.norm.weight, emb.norm.bias, emb.norm.eps, F32)
             saved = [patches, conv, mean, rstd]
-            x = ops.tokens_assemble(y, B, np_, cls_, pos_)
+            x = (ops.tokens_assemble(y, B, np_, cls_, pos_) if kp is None
+                 else ops.tokens_assemble_keep(y, np_, kp, cls_, pos_))
         ctx.save_for_backward(*saved)
         ctx.emb, ctx.cls, ctx.pos, ctx.dims = emb, cls, pos, (B, np_, D)
         ctx.img_shape = (B, C, S, P)
+        ctx.slot = keep[1] if keep is not None else None
         return x
 
     @staticmethod
     @_folds
     def backward(ctx, dx):
         emb, cls, pos, (B, np_, D) = ctx.emb, ctx.cls, ctx.pos, ctx.dims
+        slot = ctx.slot
         ps = list(emb.parameters())
-        gs = _sink(ctx, 4, ps, getattr(emb, "_arena", None), extra=[(2, cls), (3, pos)])
+        gs = _sink(ctx, 5, ps, getattr(emb, "_arena", None), extra=[(2, cls), (3, pos)])
         saved = ctx.saved_tensors
         patches = saved[0]
         T = patches.dtype
@@ -746,7 +759,10 @@ class _EmbedFn(torch.autograd.Function):
         dw = dw.view(D, -1) if dw is not None else None
         if emb.norm is not None:
             conv, mean, rstd = saved[1:]
-            dy, _ = ops.tokens_assemble_bwd(dx, B, np_, True, None, dcls, dpos)
+            if slot is None:
+                dy, _ = ops.tokens_assemble_bwd(dx, B, np_, True, None, dcls, dpos)
+            else:
+                dy, _ = ops.tokens_assemble_keep_bwd(dx, slot, True, None, dcls, dpos)
             dconv, dconv_lp = ops.layernorm_bwd(dy, conv, mean, rstd, emb.norm.weight,
                                                 gs(emb.norm.weight), gs(emb.norm.bias), lp_dtype=lpT)
             g = dconv_lp if dconv_lp is not None else dconv
@@ -756,8 +772,11 @@ class _EmbedFn(torch.autograd.Function):
                 ops.bias_grad(g, gs(emb.proj.bias))
         else:
             Bi, C, S, P = ctx.img_shape
-            ops.patch_embed_bwd(dx, patches, Bi, C, S, P, dw, gs(emb.proj.bias), dcls, dpos)
-        return (None, None, gs.grads([cls])[0], gs.grads([pos])[0]) + gs.grads(ps)
+            if slot is None:
+                ops.patch_embed_bwd(dx, patches, Bi, C, S, P, dw, gs(emb.proj.bias), dcls, dpos)
+            else:
+                ops.patch_embed_keep_bwd(dx, patches, slot, C, S, P, dw, gs(emb.proj.bias), dcls, dpos)
+        return (None, None, gs.grads([cls])[0], gs.grads([pos])[0], None) + gs.grads(ps)
 
 
 # ======================================================================= head + loss
@@ -975,6 +994,9 @@ class VisionTransformer(nn.Module):
         self._arena: Optional[ParamArena] = None
         self.drop_seed: Optional[int] = None   # fixed dropout seed (tests); None = drawn per forward
         self._fc2_bias_fused = True
+        # patch dropout: the [B, K] int32 kept patch numbers (ascending) of the last training forward,
+        # None otherwise (masked-prediction losses index their targets with it)
+        self.last_patch_keep: Optional[Tensor] = None
         self.reset_parameters()
 
     # -- init: trunc_normal(.02) weights, zero biases, LN (1, 0)  (old_codes/MS_CvT.py:437-454)
@@ -1032,13 +1054,21 @@ class VisionTransformer(nn.Module):
         if torch.is_grad_enabled():
             arena.begin_step()
         pe = self.patch_embed
-        t = _EmbedFn.apply(x, pe, self.cls_token, self.pos_embed, *pe.parameters())
+        rate = self.cfg.drop_rate
+        np_, K = self.cfg.num_patches, self.cfg.kept_patches
+        masks = rate > 0.0 or any(blk.drop_path > 0.0 for blk in self.blocks)
+        seed = _drop_seed(self, masks or K < np_)   # one draw per forward that drops anything
+        # patch dropout: the kept subset of every sample, one launch, no host read
+        keep = ops.patch_keep(x.shape[0], np_, K, seed, x.device) if seed is not None and K < np_ else None
+        self.last_patch_keep = keep[0] if keep is not None else None
+        t = _EmbedFn.apply(x, pe, self.cls_token, self.pos_embed, keep, *pe.parameters())
         # bias-grad fusion: block i's LN1 backward produces colsum(d input) = the fc2 bias grad
         # of block i-1; the head's LN backward does it for the last block.
-        rate = self.cfg.drop_rate
-        seed = _drop_seed(self, rate > 0.0 or any(blk.drop_path > 0.0 for blk in self.blocks))
         # with dropout or drop path the fc2/proj bias grads are column sums of MASKED gradients: no
-        # fusion across blocks, in any block of the model
+        # fusion across blocks, in any block of the model.  Patch dropout alone masks nothing inside
+        # a block (the blocks see a plain model with N = K + 1): the fusion stays on.
+        if not masks:
+            seed = None
         fused = self._fc2_bias_fused = seed is None
         L = len(self.blocks)
         for i, blk in enumerate(self.blocks):

@@ -535,6 +535,92 @@ def patch_embed_bwd(dx: Tensor, patches: Tensor, B: int, C: int, S: int, P: int,
                                       _p(dpos), _p(ws), ws.numel(), _s()), "patch_embed_bwd")
 
 
+# ---------------------------------------------------------------- patch dropout
+PATCH_SITE = 0x20000000   # the hash site of the patch-dropout keys (include/vitmi.h, "Patch dropout")
+
+
+def patch_keep(B: int, np_: int, K: int, seed: int, device=None):
+    """vitmi_patch_keep: (keep int32 [B, K], the kept patch numbers of every sample in ascending
+    order; slot int32 [B, np_], each patch's position in keep or -1).  No host read."""
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    keep = torch.empty(B, K, dtype=torch.int32, device=device)
+    slot = torch.empty(B, np_, dtype=torch.int32, device=device)
+    check(lib().vitmi_patch_keep(B, np_, K, seed & 0xFFFFFFFF, PATCH_SITE, _p(keep), _p(slot), _s()), "patch_keep")
+    return keep, slot
+
+
+def patch_im2col_keep(img: Tensor, P: int, keep: Tensor, out_dtype: torch.dtype) -> Tensor:
+    """patch_im2col of the kept patches only: [B*K, C*P*P], row b*K + j = patch keep[b, j]."""
+    B, C, S, S2 = img.shape
+    assert S == S2 and img.dtype == torch.float32 and img.is_contiguous()
+    assert keep.dtype == torch.int32 and keep.is_contiguous() and keep.shape[0] == B
+    K = keep.shape[1]
+    out = torch.empty(B * K, C * P * P, dtype=out_dtype, device=img.device)
+    check(lib().vitmi_patch_im2col_keep(dt(out_dtype), B, C, S, P, K, _p(keep), _p(img), _p(out), _s()),
+          "patch_im2col_keep")
+    return out
+
+
+def tokens_assemble_keep(tok: Tensor, np_: int, keep: Tensor, cls: Optional[Tensor], pos: Optional[Tensor]) -> Tensor:
+    """x [B, K+1, D]: row 0 = cls + pos[0], row 1+j = tok[b*K+j] + pos[1 + keep[b, j]]."""
+    B, K = keep.shape
+    D = tok.shape[-1]
+    assert keep.dtype == torch.int32 and keep.is_contiguous() and tok.shape[0] == B * K
+    x = torch.empty(B, K + 1, D, dtype=torch.float32, device=tok.device)
+    check(lib().vitmi_tokens_assemble_keep(B, np_, K, D, _p(tok), _p(cls), _p(pos), _p(keep), _p(x), _s()),
+          "tokens_assemble_keep")
+    return x
+
+
+def tokens_assemble_keep_bwd(dx: Tensor, slot: Tensor, want_f32: bool, lp_dtype: Optional[torch.dtype],
+                             dcls: Optional[Tensor], dpos: Optional[Tensor]):
+    """(dtok fp32, dtok in lp_dtype) [B*K, D] = dx[:, 1:]; dcls / dpos [np+1, D] += their sums over
+    the samples (dpos row 1+p over the samples that kept p, through slot)."""
+    B, np_ = slot.shape
+    K, D = dx.shape[1] - 1, dx.shape[-1]
+    assert slot.dtype == torch.int32 and slot.is_contiguous() and dx.shape[0] == B
+    dtok = torch.empty(B * K, D, dtype=torch.float32, device=dx.device) if want_f32 else None
+    dtok_lp = None
+    if lp_dtype is not None and lp_dtype != torch.float32:
+        dtok_lp = torch.empty(B * K, D, dtype=lp_dtype, device=dx.device)
+    check(lib().vitmi_tokens_assemble_keep_bwd(B, np_, K, D, _p(dx.contiguous()), _p(dtok), _p(dtok_lp), _p(dcls),
+                                               _p(dpos), _p(slot), _s()), "tokens_assemble_keep_bwd")
+    return dtok, dtok_lp
+
+
+def patch_embed_keep_fwd(img: Tensor, w: Tensor, bias: Optional[Tensor], cls: Optional[Tensor],
+                         pos: Optional[Tensor], P: int, keep: Tensor, dtype: torch.dtype):
+    """vitmi_patch_embed_keep_fwd: patch_embed_fwd over the kept patches -> (x fp32 [B, K+1, D],
+    patches [B*K, C*P*P] of dtype, saved for the backward)."""
+    B, C, S, S2 = img.shape
+    assert S == S2 and img.dtype == torch.float32 and img.is_contiguous()
+    D = w.shape[0]
+    assert w.is_contiguous() and w.dtype == dtype and w.shape[1] == C * P * P
+    assert keep.dtype == torch.int32 and keep.is_contiguous() and keep.shape[0] == B
+    K = keep.shape[1]
+    patches = torch.empty(B * K, C * P * P, dtype=dtype, device=img.device)
+    x = torch.empty(B, K + 1, D, dtype=torch.float32, device=img.device)
+    ws = _ws(lib().vitmi_patch_embed_keep_fwd_workspace_size(dt(dtype), B, C, S, P, D, K), img)
+    check(lib().vitmi_patch_embed_keep_fwd(dt(dtype), B, C, S, P, D, K, _p(keep), _p(img), _p(w), _p(bias), _p(cls),
+                                           _p(pos), _p(patches), _p(x), _p(ws), ws.numel(), _s()),
+          "patch_embed_keep_fwd")
+    return x, patches
+
+
+def patch_embed_keep_bwd(dx: Tensor, patches: Tensor, slot: Tensor, C: int, S: int, P: int, dw: Optional[Tensor],
+                         dbias: Optional[Tensor], dcls: Optional[Tensor], dpos: Optional[Tensor]) -> None:
+    """vitmi_patch_embed_keep_bwd: dw [D, C*P*P] / dbias / dcls / dpos [np+1, D] (fp32) += their
+    gradients from dx [B, K+1, D]."""
+    dx = dx.contiguous()
+    B, K, D = dx.shape[0], dx.shape[1] - 1, dx.shape[-1]
+    assert slot.dtype == torch.int32 and slot.is_contiguous() and slot.shape[0] == B
+    dtype = patches.dtype
+    ws = _ws(lib().vitmi_patch_embed_keep_bwd_workspace_size(dt(dtype), B, C, S, P, D, K), dx)
+    check(lib().vitmi_patch_embed_keep_bwd(dt(dtype), B, C, S, P, D, K, _p(slot), _p(dx), _p(patches), _p(dw),
+                                           _p(dbias), _p(dcls), _p(dpos), _p(ws), ws.numel(), _s()),
+          "patch_embed_keep_bwd")
+
+
 def linear_bwd(dy: Tensor, x: Optional[Tensor], w: Optional[Tensor], dx_dtype: Optional[torch.dtype],
                dw: Optional[Tensor], db: Optional[Tensor]) -> Optional[Tensor]:
     """vitmi_linear_bwd: dx = dy W (when dx_dtype), dw += dy^T x, db += colsum(dy)."""
