@@ -81,13 +81,32 @@ def test_linear_dgrad(M, N, K, T, policy):
     assert rel(dg.float(), gl) < (8e-3 if T == BF else 1e-5)
 
 
-@pytest.mark.parametrize("M,N,K", [(256 * 9, 256, 768), (256 * 8 + 100, 256 + 64, 512), (256 * 17, 256, 256)])
+def _kernel_calls(substring):
+    """Launches recorded since vitmi_stats_enable(1) of the kernels whose mangled name contains
+    ``substring``."""
+    import ctypes
+    from vitmi._lib import lib
+    n = 0
+    for i in range(lib().vitmi_stats_count()):
+        name = ctypes.create_string_buffer(1024)
+        calls, fl, by = ctypes.c_int64(0), ctypes.c_double(0), ctypes.c_double(0)
+        lib().vitmi_stats_get(i, name, 1024, ctypes.byref(calls), ctypes.byref(fl), ctypes.byref(by))
+        if substring in name.value.decode():
+            n += calls.value
+    return n
+
+
+@pytest.mark.parametrize("M,N,K", [(256 * 9, 256, 768), (256 * 8 + 100, 256 + 64, 512), (256 * 17, 256, 256),
+                                   (256 * 9, 256, 1024)])
 def test_gemm_tail_split(M, N, K):
     """Persistent gemm256 on an 8-block grid (policy 3): the tiles of an under-filled last
-    round are split over K into fp32 partials + fix-up kernel.  Every epilogue goes through
-    the fix-up path; the workspace query must size it."""
+    round are split over K into fp32 partials + fix-up kernel.  At K = 1024 (16 K-steps,
+    VITMI_TAIL_MINK) every epilogue goes through the fix-up path; below that only DGELU
+    tail-splits (Epi::tail_min_ksteps): asserted through the kernel statistics.  The workspace
+    query must size it."""
     from vitmi._lib import lib
     lib().vitmi_gemm_set_policy(3)
+    lib().vitmi_stats_enable(1)
     try:
         assert lib().vitmi_linear_fwd_workspace_size(1, M, N, K) > 0
         x, w, b = rnd(M, K, dtype=BF, seed=41), rnd(N, K, dtype=BF, seed=42, scale=0.05), rnd(N, seed=43)
@@ -106,7 +125,11 @@ def test_gemm_tail_split(M, N, K):
         gpv = gelu_grad(rnd(M, N, seed=47)).to(BF)
         dx = ops.linear_dgrad(dy.to(DEV), w2.to(DEV), BF, ops.EPI_DGELU, aux=gpv.to(DEV))
         assert rel(dx.float(), ref * gpv.float()) < 8e-3
+        # store, GELU, residual and DGELU each ran one gemm256 launch; which of them split the tail
+        assert _kernel_calls("gemm256_kernel") == 4
+        assert _kernel_calls("gemm_tail_fixup_kernel") == (4 if K >= 1024 else 1)
     finally:
+        lib().vitmi_stats_enable(0)
         lib().vitmi_gemm_set_policy(0)
 
 

@@ -1983,8 +1983,9 @@ static int gemm_impl(GemmReq q) {
   splits = (int)((K + g.k_per_split - 1) / g.k_per_split);
   if (splits < 1) splits = 1;
   if (splits > 1) {
+    // (the reduce kernels add the slabs onto a dense C: a pitched C takes the unsplit launch)
     const size_t need = (size_t)splits * M * N * sizeof(float);
-    if (q.ws == nullptr || q.ws_bytes < need) splits = 1, g.k_per_split = ktiles * BK;
+    if (q.ws == nullptr || q.ws_bytes < need || g.ldc != N) splits = 1, g.k_per_split = ktiles * BK;
   }
   bool big_ok = big;
   if (big_ok) {
@@ -2021,7 +2022,6 @@ static int gemm_impl(GemmReq q) {
   GemmArgs gp = g;
   gp.C = q.ws; gp.ldc = N; gp.split_stride = M * N;
   if (int rc = run(EpiPartial::code, VITMI_F32, gp, splits)) return rc;
-  VITMI_CHECK_ARG(g.ldc == N, "gemm: split-K accumulate needs a dense C");
   const int64_t n = M * N;
   if ((n + 3) / 4 <= SMALL_RED_MAX && splits >= 16) {
     hipLaunchKernelGGL(splitk_reduce_small_kernel, dim3((unsigned)(((n + 3) / 4 + 63) / 64)), dim3(1024), 0, q.s,
