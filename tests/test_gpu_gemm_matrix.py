@@ -16,7 +16,6 @@ rows, 8 ragged columns) over two K-steps; *tail* 515 x 520 x 1024, 9 tiles on po
 (ntail 1, S 4, 16 K-steps: every tail-splitting epilogue goes through gemm_tail_fixup_kernel),
 645 x 648 (the same plan with a 133 x 136 tail tile) and 515 x 776 (12 tiles: ntail 4, S 2); *small* M = 1, N = 1, N % 8 != 0 and the one-K-step fallback;
 *split-K* a 136 x 136 output over a 4000-long reduction."""
-import ctypes
 from dataclasses import dataclass
 from functools import lru_cache
 
@@ -26,6 +25,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import ref_gemm as rg  # noqa: E402
+from kstats import kernel_stats  # noqa: E402
 from vitmi import _lib  # noqa: E402
 
 DEV = "cuda"
@@ -36,7 +36,7 @@ EPI = {"store": 0, "gelu": 1, "residual": 2, "dgelu": 3, "accum": 4}
 AUX_TILED, SPLIT_X3, SPLIT_F8 = 0x100, 0x200, 0x400
 VITMI_BF16F8, VITMI_BF16F8W = 4, 5
 PATH_SITE, DROP_SITE, RATE_DROP, RATE_PATH = 0x40000003, 4, 0.25, 0.5
-TAIL_SMAX, TAIL_MINK = 4, 16     # csrc/gemm.hip VITMI_TAIL_SMAX / VITMI_TAIL_MINK
+TAIL_SMAX, TAIL_MINK = 4, 16     # csrc/gemm.hip TAIL_SMAX / TAIL_MINK
 
 L_FWD = ("KK",)
 L_3 = ("KK", "KN", "NN")
@@ -200,34 +200,6 @@ def plan(base, bf16, M, N, Kred, pol, tail_split, f8=False, ws="query", dense_c=
         p["fixup"] = (tp is not None and p["big"] and tail_split and ws == "query"
                       and nk >= (0 if base == "dgelu" else TAIL_MINK))
     return p
-
-
-class kernel_stats:
-    """vitmi_stats_enable(1) around a block; .calls(substring) afterwards."""
-
-    def __enter__(self):
-        _lib.lib().vitmi_stats_enable(1)
-        self.k = {}
-        return self
-
-    def __exit__(self, *exc):
-        lib = _lib.lib()
-        try:
-            for i in range(lib.vitmi_stats_count()):
-                name = ctypes.create_string_buffer(1024)
-                calls, fl, by = ctypes.c_int64(0), ctypes.c_double(0), ctypes.c_double(0)
-                lib.vitmi_stats_get(i, name, 1024, ctypes.byref(calls), ctypes.byref(fl), ctypes.byref(by))
-                self.k[name.value.decode()] = calls.value
-        finally:
-            lib.vitmi_stats_enable(0)
-        return False
-
-    def calls(self, sub):
-        return sum(c for n, c in self.k.items() if sub in n)
-
-    def summary(self):
-        return {s: self.calls(s) for s in ("gemm_kernel", "gemm256_kernel", "gemm_tail_fixup_kernel", "splitk_reduce")
-                if self.calls(s)}
 
 
 def assert_kernels(st, p, what):

@@ -101,7 +101,7 @@ def _kernel_calls(substring):
 def test_gemm_tail_split(M, N, K):
     """Persistent gemm256 on an 8-block grid (policy 3): the tiles of an under-filled last
     round are split over K into fp32 partials + fix-up kernel.  At K = 1024 (16 K-steps,
-    VITMI_TAIL_MINK) every epilogue goes through the fix-up path; below that only DGELU
+    TAIL_MINK) every epilogue goes through the fix-up path; below that only DGELU
     tail-splits (Epi::tail_min_ksteps): asserted through the kernel statistics.  The workspace
     query must size it."""
     from vitmi._lib import lib

@@ -26,11 +26,8 @@
 namespace vitmi {
 
 static constexpr int DH = 64;
-// backward kernels: dP - delta formed by the MFMA chain (accumulator initialised to
-// -delta) instead of a subtraction per element (0: the subtraction; A/B builds)
-#ifndef VITMI_ATT_DPINIT
-#define VITMI_ATT_DPINIT 1
-#endif
+// (backward kernels: dP - delta is formed by the MFMA chain, its accumulator initialised to
+// -delta, instead of a subtraction per element)
 static constexpr float LOG2E = 1.4426950408889634f;
 static constexpr float LN2 = 0.6931471805599453f;
 
@@ -466,7 +463,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkv_bf16(
           L2[g4] = *(const f32x4*)(rl + q4);
           const f32x4 dl = *(const f32x4*)(rl + 64 + q4);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) dp[4 * g4 + i] = VITMI_ATT_DPINIT ? -dl[i] : 0.f;
+          for (int i = 0; i < 4; ++i) dp[4 * g4 + i] = -dl[i];
         }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -475,12 +472,11 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkv_bf16(
         }
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
-          [[maybe_unused]] const f32x4 dl = VITMI_ATT_DPINIT ? f32x4{} : *(const f32x4*)(rl + 64 + 32 * u + 8 * g4 + 4 * h);
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const float p = fexp2(sa[4 * g4 + i] * c2 - L2[g4][i]);
             sa[4 * g4 + i] = p;
-            dp[4 * g4 + i] = VITMI_ATT_DPINIT ? p * dp[4 * g4 + i] : p * (dp[4 * g4 + i] - dl[i]);
+            dp[4 * g4 + i] = p * dp[4 * g4 + i];
           }
         }
         // dV^T[d][key] += dO^T[d][q] P[q][key];  dK^T[d][key] += Q^T[d][q] dS[q][key]
@@ -586,7 +582,7 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_bf16(
       for (int u = 0; u < 2; ++u) {  // 32-key sub-tile
         if (t * 64 + 32 * u >= N) break;   // all 32 keys padding: dS = 0 there
         f32x16 st = zero16(), dp;
-        float ndl = VITMI_ATT_DPINIT ? -dl : 0.f;   // dP^T - delta from the MFMA chain
+        float ndl = -dl;   // dP^T - delta from the MFMA chain
         asm volatile("" : "+v"(ndl));                // (splat formed here, not hoisted)
 #pragma unroll
         for (int r = 0; r < 16; ++r) dp[r] = ndl;
@@ -603,7 +599,7 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_bf16(
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float p = fexp2(fmaf(st[r], c2, -L2));   // q >= N: L2 = +inf -> p = 0
-          dp[r] = VITMI_ATT_DPINIT ? p * dp[r] : p * (dp[r] - dl);
+          dp[r] = p * dp[r];
         }
         // dQ^T[d][q] += K^T[d][key] dS^T[key][q]
 #pragma unroll
@@ -867,9 +863,6 @@ __global__ __launch_bounds__(NPMAX * 2, 4) void attn_fwd_seq_bf16(const bf16* __
   }
 }
 
-#ifndef VITMI_ATTN_Q64
-#define VITMI_ATTN_Q64 1
-#endif
 // The bf16 forward (vitmi_attention_fwd, N <= 256) with 4 waves of 64 queries (two 32-query
 // blocks per wave): every K and V fragment read from LDS feeds both blocks' MFMAs, and each wave
 // carries two independent softmax chains.  Per query block the arithmetic is attn_fwd_seq_bf16's,
@@ -1116,7 +1109,7 @@ __global__ __launch_bounds__(NPMAX * 2, 4) void attn_bwd_dq_seq_bf16(
     // constant per lane), so dS = P (dP - delta) is one multiply per element
     // (the opaque copy keeps the 16-register splat inside the block: hoisted out of the
     // unrolled key loop it stays live across it and pushes the kernel past 128 VGPRs)
-    float ndl = VITMI_ATT_DPINIT ? -dl : 0.f;
+    float ndl = -dl;
     asm volatile("" : "+v"(ndl));
 #pragma unroll
     for (int r = 0; r < 16; ++r) dp[r] = ndl;
@@ -1128,7 +1121,7 @@ __global__ __launch_bounds__(NPMAX * 2, 4) void attn_bwd_dq_seq_bf16(
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float p = fexp2(fmaf(st[r], c2, -L2));
-      dp[r] = VITMI_ATT_DPINIT ? p * dp[r] : p * (dp[r] - dl);
+      dp[r] = p * dp[r];
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -1232,7 +1225,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_seq64_bf16(
 #pragma unroll
       for (int qb = 0; qb < QB; ++qb) {
         st[qb] = zero16();
-        float ndl = VITMI_ATT_DPINIT ? -dl[qb] : 0.f;
+        float ndl = -dl[qb];
         asm volatile("" : "+v"(ndl));
 #pragma unroll
         for (int r = 0; r < 16; ++r) dp[qb][r] = ndl;
@@ -1251,7 +1244,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_seq64_bf16(
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float p = fexp2(fmaf(st[qb][r], c2, -L2[qb]));
-          dp[qb][r] = VITMI_ATT_DPINIT ? p * dp[qb][r] : p * (dp[qb][r] - dl[qb]);
+          dp[qb][r] = p * dp[qb][r];
         }
 #pragma unroll
       for (int s = 0; s < 2; ++s)
@@ -1404,7 +1397,7 @@ __global__ __launch_bounds__(NPMAX * 2) void attn_bwd_dkv_seq_bf16(
         L2[g4] = *(const f32x4*)(l2s + q4);
         const f32x4 dl = *(const f32x4*)(dls + q4);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) dp[4 * g4 + i] = VITMI_ATT_DPINIT ? -dl[i] : 0.f;
+        for (int i = 0; i < 4; ++i) dp[4 * g4 + i] = -dl[i];
       }
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
@@ -1413,12 +1406,11 @@ __global__ __launch_bounds__(NPMAX * 2) void attn_bwd_dkv_seq_bf16(
       }
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
-        [[maybe_unused]] const f32x4 dl = VITMI_ATT_DPINIT ? f32x4{} : *(const f32x4*)(dls + q0 + 8 * g4 + 4 * h);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const float p = fexp2(fmaf(sa[4 * g4 + i], c2, -L2[g4][i]));
           sa[4 * g4 + i] = p;
-          dp[4 * g4 + i] = VITMI_ATT_DPINIT ? p * dp[4 * g4 + i] : p * (dp[4 * g4 + i] - dl[i]);
+          dp[4 * g4 + i] = p * dp[4 * g4 + i];
         }
       }
 #pragma unroll
@@ -1543,33 +1535,17 @@ __global__ __launch_bounds__(NKB * 64) void attn_bwd_fused_seq_bf16(
     const int b = bh / H, hd = bh - b * H;
     stage_seq_dma(dt_, make_rsrc(dout + (int64_t)b * N * D + hd * DH, obytes - hd * DH * 2), ldo, NP, NKB, wave, lane);
   };
-// Where the next pair's loads go (round 6, profiles/r06_pf5/): 5 = the O rows right after delta (their
-// last use), the dO image DMA and the K / V rows + lse after phase 1.  Each lane's 16-B row pieces
-// touch 32 lines per instruction, and the cost of those loads (~1.5 us per 4 instructions per wave)
-// lands in whichever phase follows their issue; the O rows hide behind the delta barrier and phase 1
-// (per layer 212-219 vs 234-243 us).  1 = all of them after phase 1, 0 = after phase 2, 2 / 3 = the
-// DMA / the register rows after phase 2, 6 / 7 = K / V spread over phase 2 (and O over phase 1):
-// measured, not better than 5.
-#ifndef VITMI_FUSED_PF
-#define VITMI_FUSED_PF 5
-#endif
-  // the O rows alone (VITMI_FUSED_PF 5 issues them right after delta, their last use)
-  auto load_o = [&](int bh, bf16x8 (&of)[4], int s0 = 0, int s1 = 4) {
+  // Where the next pair's loads go (profiles/r06_pf5/): the O rows right after delta (their last
+  // use), the dO image DMA and the K / V rows + lse after phase 1.  Each lane's 16-B row pieces touch
+  // 32 lines per instruction, and the cost of those loads (~1.5 us per 4 instructions per wave) lands
+  // in whichever phase follows their issue; the O rows hide behind the delta barrier and phase 1 (per
+  // layer 212-219 us, vs 234-243 us with all of them after phase 1).
+  auto load_o = [&](int bh, bf16x8 (&of)[4]) {
     const int b = bh / H, hd = bh - b * H;
     const __amdgpu_buffer_rsrc_t ro = make_rsrc(o + (int64_t)b * N * D + hd * DH, obytes - hd * DH * 2);
     const uint32_t ooff = (uint32_t)((int64_t)r32 * ldo + 16 * h);
 #pragma unroll
-    for (int s = s0; s < s1; ++s) of[s] = __builtin_bit_cast(bf16x8, asm_load16(ro, ooff, 32 * s));
-  };
-  // one 16-B piece of the lane's K and V rows (VITMI_FUSED_PF 6 spreads them over phase 2)
-  auto load_kv1 = [&](int bh, bf16x8 (&kf)[4], bf16x8 (&vf)[4], int s) {
-    const int b = bh / H, hd = bh - b * H;
-    const bf16* base = qkv + (int64_t)b * N * ld;
-    const __amdgpu_buffer_rsrc_t rk = make_rsrc(base + D + hd * DH, bytes - (D + hd * DH) * 2);
-    const __amdgpu_buffer_rsrc_t rv = make_rsrc(base + 2 * D + hd * DH, bytes - (2 * D + hd * DH) * 2);
-    const uint32_t kvoff = (uint32_t)((int64_t)r32 * ldb + 16 * h);
-    kf[s] = __builtin_bit_cast(bf16x8, asm_load16(rk, kvoff, 32 * s));
-    vf[s] = __builtin_bit_cast(bf16x8, asm_load16(rv, kvoff, 32 * s));
+    for (int s = 0; s < 4; ++s) of[s] = __builtin_bit_cast(bf16x8, asm_load16(ro, ooff, 32 * s));
   };
   auto load_regs = [&](int bh, bf16x8 (&kf)[4], bf16x8 (&vf)[4], bf16x8 (&of)[4], float& ls, bool with_o = true) {
     const int b = bh / H, hd = bh - b * H;
@@ -1626,9 +1602,7 @@ __global__ __launch_bounds__(NKB * 64) void attn_bwd_fused_seq_bf16(
         if (ok) delta[(int64_t)bh * N + r32] = dl;
       }
     }
-    const bool more1 = i + (int)gridDim.x < npairs;
-    const int nbh1 = more1 ? pair_of(i + gridDim.x) : 0;
-    if ((VITMI_FUSED_PF == 5 || VITMI_FUSED_PF == 6) && more1) load_o(pair_of(i + gridDim.x), of);   // (of is dead)
+    if (i + (int)gridDim.x < npairs) load_o(pair_of(i + gridDim.x), of);   // (of is dead)
     __syncthreads();
     FUSED_STAMP(bh, 1);
 
@@ -1639,7 +1613,6 @@ __global__ __launch_bounds__(NKB * 64) void attn_bwd_fused_seq_bf16(
       const int q0 = 32 * qb;
       f32x16 sa = zero16(), dp;
       f32x4 L2[4];
-      if (VITMI_FUSED_PF == 7 && more1 && qb < 4) load_o(nbh1, of, qb, qb + 1);   // (of is dead after delta)
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const int q4 = q0 + 8 * g4 + 4 * h;
@@ -1690,21 +1663,11 @@ __global__ __launch_bounds__(NKB * 64) void attn_bwd_fused_seq_bf16(
     const int inext = i + gridDim.x;
     const bool more = inext < npairs;
     const int nbh = more ? pair_of(inext) : 0;
-    // the next pair's dO image (the dO image is free) and register rows (kf / vf / of are dead)
-    // land under phase 2 and the epilogue
-    if (more && VITMI_FUSED_PF == 1) {
-      stage_do(nbh);
-      load_regs(nbh, kf, vf, of, ls);
-    }
-    if (more && VITMI_FUSED_PF == 2) load_regs(nbh, kf, vf, of, ls);
-    if (more && VITMI_FUSED_PF == 3) stage_do(nbh);
-    if (more && VITMI_FUSED_PF == 5) {
+    // the next pair's dO image (the dO image is free) and K / V rows + lse (kf / vf are dead) land
+    // under phase 2 and the epilogue
+    if (more) {
       stage_do(nbh);
       load_regs(nbh, kf, vf, of, ls, false);
-    }
-    if (more && (VITMI_FUSED_PF == 6 || VITMI_FUSED_PF == 7)) {
-      stage_do(nbh);
-      ls = asm_load4(make_rsrc(lse + (int64_t)nbh * N, (uint32_t)N * 4), (uint32_t)r32 * 4);
     }
     __syncthreads();
 
@@ -1713,7 +1676,6 @@ __global__ __launch_bounds__(NKB * 64) void attn_bwd_fused_seq_bf16(
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {
       const char* tile = dst + (kb * NKB + wave) * DT;
-      if ((VITMI_FUSED_PF == 6 || VITMI_FUSED_PF == 7) && more && kb < 4) load_kv1(nbh, kf, vf, kb);
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         const bf16x8 sf = frag_tr32(tile, 16 * s, lane);
@@ -1724,12 +1686,6 @@ __global__ __launch_bounds__(NKB * 64) void attn_bwd_fused_seq_bf16(
     __syncthreads();   // the K image is free (the next Q lands there); dS^T area -> output images
     FUSED_STAMP(bh, 3);
     if (more) stage_q(nbh);
-    if (more && VITMI_FUSED_PF == 0) {
-      stage_do(nbh);
-      load_regs(nbh, kf, vf, of, ls);
-    }
-    if (more && VITMI_FUSED_PF == 2) stage_do(nbh);
-    if (more && VITMI_FUSED_PF == 3) load_regs(nbh, kf, vf, of, ls);
 
     // ---- epilogue: dQ, dK, dV through three images per wave, then their column sums (the q/k/v
     // bias-gradient partials of this batch row) in one pass, folded in wave order
@@ -2257,15 +2213,49 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_f32(const float* __restrict_
 
 using namespace vitmi;
 
-// whole-sequence kernels for N <= SEQ_MAX (8 waves, 2 workgroups of <= 64 KiB LDS per CU).
+// ---------------------------------------------------------------- host side
+// Every entry point asks attn_plan once which kernels run, and every kernel is launched (and its
+// algorithmic work recorded) by one `launch` call.
+// Whole-sequence kernels for N <= SEQ_MAX (8 waves, 2 workgroups of <= 64 KiB LDS per CU).
 // Kernel policy (vitmi_attention_set_policy; tests): 0 = auto, 1 = always the streamed kernels,
 // 2 = the whole-sequence 32-query-per-wave forward / dQ (attn_fwd_seq_bf16 / attn_bwd_dq_seq_bf16)
 // where auto takes their 64-query forms (bitwise equal by construction; the tests compare them),
 // and the two-kernel backward; 3 = auto's forward with the two-kernel backward (64-query dQ, then
 // dK/dV) where auto runs the single-pass attn_bwd_fused_seq_bf16 (N <= 224).
 static constexpr int SEQ_MAX = 256;
+static constexpr int FUSED_NKB = 7;   // the single-pass backward's LDS holds NKB^2 dS^T tiles: N <= 224
+static int g_attn_policy = 0;
 
-static int device_cus() {   // compute units of the current device (the persistent dK/dV grid)
+enum AttnPath { STREAM_BF16, SEQ_BF16, SEQ_F32, STREAM_F32 };
+struct AttnPlan {
+  AttnPath path;
+  bool q64;          // SEQ_BF16: the 64-query forward / dQ forms
+  bool fused;        // SEQ_BF16: the single-pass backward
+  int nkb;           // ceil(N / 32): waves of the 32-query forms, NKB of the single-pass backward
+  int colsum_rows;   // bias-gradient partial rows per batch that the backward kernels form (0: none)
+};
+static AttnPlan attn_plan(int dtype, int N) {
+  const bool bf = dtype == VITMI_BF16, seq = N <= SEQ_MAX && g_attn_policy != 1;
+  AttnPlan p;
+  p.path = bf ? (seq ? SEQ_BF16 : STREAM_BF16) : (seq ? SEQ_F32 : STREAM_F32);
+  p.nkb = (N + 31) / 32;
+  p.q64 = g_attn_policy != 2;
+  p.fused = g_attn_policy == 0 && p.nkb <= FUSED_NKB;
+  // one row per batch (whole-sequence kernels) or per (batch, 128-row block); the fp32 kernels form none
+  p.colsum_rows = !bf ? 0 : seq ? 1 : (N + 127) / 128;
+  return p;
+}
+// the largest colsum_rows over all policies (the policy may change between a workspace query and the call)
+static int attn_colsum_rows_max(int N) { return (N + 127) / 128; }
+
+// one launch and its VITMI_STAT record, both from the same kernel symbol
+template <typename... P, typename... A>
+static void launch(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t s, double flops, double bytes, A... args) {
+  hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
+  VITMI_STAT(kernel, flops, bytes);
+}
+
+static int device_cus() {   // compute units of the current device (the persistent backward grids)
   static int cus = 0;
   if (cus == 0) {
     int dev = 0, n = 0;
@@ -2276,28 +2266,6 @@ static int device_cus() {   // compute units of the current device (the persiste
       cus = 256;
   }
   return cus;
-}
-static int g_attn_policy = 0;
-static bool seq_path(int N) { return N <= SEQ_MAX && g_attn_policy != 1; }
-static bool q64() { return VITMI_ATTN_Q64 && g_attn_policy != 2; }
-#ifndef VITMI_ATTN_FUSED_BWD
-#define VITMI_ATTN_FUSED_BWD 1
-#endif
-static constexpr int FUSED_NKB = 7;   // the single-pass backward's LDS holds NKB^2 dS^T tiles: N <= 224
-static bool fused_bwd(int N) { return VITMI_ATTN_FUSED_BWD && g_attn_policy == 0 && (N + 31) / 32 <= FUSED_NKB; }
-
-template <int NKB>
-static void launch_fused(int B, int N, int H, float scale, const void* qkv, const void* o, const void* dout,
-                         const float* lse, float* delta, void* dqkv, float* colsum, hipStream_t s) {
-  // persistent: one workgroup per CU (its LDS), each walking the (batch, head) pairs
-  const int npairs = B * H, cus = device_cus();
-  hipLaunchKernelGGL(attn_bwd_fused_seq_bf16<NKB>, dim3(npairs < cus ? npairs : cus), dim3(64 * NKB), 0, s,
-                     (const bf16*)qkv, (const bf16*)o, (const bf16*)dout, lse, delta, (bf16*)dqkv, N, H, scale,
-                     colsum, npairs);
-  // algorithmic backward = dP, dQ, dV, dK: 8 N^2 dh flops per head (recomputing S is not counted);
-  // bytes: q/k/v/o/dO read and dq/dk/dv written once, lse read and delta written
-  const double bh = (double)B * H, t = bh * N * DH;
-  VITMI_STAT(attn_bwd_fused_seq_bf16<NKB>, 8.0 * bh * N * N * DH, t * 8 * 2 + bh * N * 8);
 }
 
 extern "C" int vitmi_attention_set_policy(int policy) {
@@ -2316,40 +2284,48 @@ static int attn_check(int dtype, int B, int N, int H, int dh) {
   return VITMI_OK;
 }
 
+// The forward of all three entry points.  XM (the precision knobs): 1 also writes ox = o3, 2 ox = o8
+// (attn_fwd_seq64_bf16's note); those exist only in the whole-sequence bf16 kernels (their entry
+// points refuse N > SEQ_MAX), so policy 1 does not apply to them.
+template <int XM>
+static int attention_fwd_launch(const char* what, int dtype, int B, int N, int H, float scale, const void* qkv,
+                                void* o, void* ox, float* lse, hipStream_t s) {
+  AttnPlan p = attn_plan(dtype, N);
+  if (XM) p.path = SEQ_BF16;
+  // QK^T and PV: 4 N^2 dh flops per (batch, head); q/k/v read, o (+ the 3 or 2 row parts of ox) + lse written
+  const double es = dtype == VITMI_BF16 ? 2 : 4, bh = (double)B * H;
+  const double fl = 4.0 * bh * N * N * DH, by = bh * N * DH * (4 + (XM == 1 ? 3 : XM == 2 ? 2 : 0)) * es + bh * N * 4;
+  switch (p.path) {
+    case SEQ_BF16:
+      if (p.q64)
+        launch(attn_fwd_seq64_bf16<SEQ_MAX, XM>, dim3(B * H), dim3(256), s, fl, by, (const bf16*)qkv, (bf16*)o, lse, N,
+               H, scale, (bf16*)ox);
+      else
+        launch(attn_fwd_seq_bf16<SEQ_MAX, XM>, dim3(B * H), dim3(64 * p.nkb), s, fl, by, (const bf16*)qkv, (bf16*)o,
+               lse, N, H, scale, (bf16*)ox);
+      break;
+    case STREAM_BF16:
+      launch(attn_fwd_bf16, dim3((N + 127) / 128, B * H), dim3(256), s, fl, by, (const bf16*)qkv, (bf16*)o, lse, N, H,
+             scale);
+      break;
+    case SEQ_F32:
+      launch(attn_fwd_seq_f32<SEQ_MAX>, dim3(B * H), dim3(64 * p.nkb), s, fl, by, (const float*)qkv, (float*)o, lse, N,
+             H, scale);
+      break;
+    case STREAM_F32:
+      launch(attn_fwd_f32, dim3((N + 63) / 64, B * H), dim3(256), s, fl, by, (const float*)qkv, (float*)o, lse, N, H,
+             scale);
+      break;
+  }
+  VITMI_LAUNCH_CHECK(what);
+  return VITMI_OK;
+}
+
 extern "C" int vitmi_attention_fwd(int dtype, int B, int N, int H, int dh, float scale,
                                    const void* qkv, void* o, float* lse, vitmi_stream_t stream) {
   if (int rc = attn_check(dtype, B, N, H, dh)) return rc;
   VITMI_CHECK_ARG(qkv && o && lse, "attention_fwd: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == VITMI_BF16 && seq_path(N) && q64()) {
-    hipLaunchKernelGGL(attn_fwd_seq64_bf16<SEQ_MAX>, dim3(B * H), dim3(256), 0, s, (const bf16*)qkv, (bf16*)o, lse,
-                       N, H, scale);
-  } else if (dtype == VITMI_BF16 && seq_path(N)) {
-    const dim3 block(64 * ((N + 31) / 32));
-    hipLaunchKernelGGL(attn_fwd_seq_bf16<SEQ_MAX>, dim3(B * H), block, 0, s, (const bf16*)qkv, (bf16*)o, lse, N,
-                       H, scale);
-  } else if (dtype == VITMI_BF16) {
-    dim3 grid((N + 127) / 128, B * H);
-    hipLaunchKernelGGL(attn_fwd_bf16, grid, dim3(256), 0, s, (const bf16*)qkv, (bf16*)o, lse, N, H, scale);
-  } else if (seq_path(N)) {
-    hipLaunchKernelGGL(attn_fwd_seq_f32<SEQ_MAX>, dim3(B * H), dim3(64 * ((N + 31) / 32)), 0, s, (const float*)qkv,
-                       (float*)o, lse, N, H, scale);
-  } else {
-    dim3 grid((N + 63) / 64, B * H);
-    hipLaunchKernelGGL(attn_fwd_f32, grid, dim3(256), 0, s, (const float*)qkv, (float*)o, lse, N, H, scale);
-  }
-  VITMI_LAUNCH_CHECK("attention_fwd");
-  {
-    // QK^T and PV: 4 N^2 dh flops per (batch, head); q/k/v read, o + lse written
-    const double es = dtype == VITMI_BF16 ? 2 : 4, bh = (double)B * H;
-    const double fl = 4.0 * bh * N * N * DH, by = bh * N * DH * 4 * es + bh * N * 4;
-    if (dtype == VITMI_BF16 && seq_path(N) && q64()) VITMI_STAT(attn_fwd_seq64_bf16<SEQ_MAX>, fl, by);
-    else if (dtype == VITMI_BF16 && seq_path(N)) VITMI_STAT(attn_fwd_seq_bf16<SEQ_MAX>, fl, by);
-    else if (dtype == VITMI_BF16) VITMI_STAT(attn_fwd_bf16, fl, by);
-    else if (seq_path(N)) VITMI_STAT(attn_fwd_seq_f32<SEQ_MAX>, fl, by);
-    else VITMI_STAT(attn_fwd_f32, fl, by);
-  }
-  return VITMI_OK;
+  return attention_fwd_launch<0>("attention_fwd", dtype, B, N, H, scale, qkv, o, nullptr, lse, (hipStream_t)stream);
 }
 
 extern "C" int vitmi_attention_fwd_x3(int B, int N, int H, int dh, float scale, const void* qkv, void* o, void* o3,
@@ -2357,19 +2333,7 @@ extern "C" int vitmi_attention_fwd_x3(int B, int N, int H, int dh, float scale, 
   if (int rc = attn_check(VITMI_BF16, B, N, H, dh)) return rc;
   VITMI_CHECK_ARG(N <= SEQ_MAX, "attention_fwd_x3: N must be <= %d (the whole-sequence kernel)", SEQ_MAX);
   VITMI_CHECK_ARG(qkv && o && o3 && lse, "attention_fwd_x3: null pointer");
-  VITMI_CHECK_ARG((int64_t)N * 3 * H * DH * 2 < 0x7fffffffLL, "attention_fwd_x3: one batch row block exceeds 2 GiB");
-  const double bh = (double)B * H, fl = 4.0 * bh * N * N * DH, by = bh * N * DH * 2 * (3 + 1 + 3) + bh * N * 4;
-  if (q64()) {
-    hipLaunchKernelGGL((attn_fwd_seq64_bf16<SEQ_MAX, 1>), dim3(B * H), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16*)qkv, (bf16*)o, lse, N, H, scale, (bf16*)o3);
-    VITMI_STAT((attn_fwd_seq64_bf16<SEQ_MAX, 1>), fl, by);
-  } else {
-    hipLaunchKernelGGL((attn_fwd_seq_bf16<SEQ_MAX, 1>), dim3(B * H), dim3(64 * ((N + 31) / 32)), 0,
-                       (hipStream_t)stream, (const bf16*)qkv, (bf16*)o, lse, N, H, scale, (bf16*)o3);
-    VITMI_STAT((attn_fwd_seq_bf16<SEQ_MAX, 1>), fl, by);
-  }
-  VITMI_LAUNCH_CHECK("attention_fwd_x3");
-  return VITMI_OK;
+  return attention_fwd_launch<1>("attention_fwd_x3", VITMI_BF16, B, N, H, scale, qkv, o, o3, lse, (hipStream_t)stream);
 }
 
 extern "C" int vitmi_attention_fwd_f8(int B, int N, int H, int dh, float scale, const void* qkv, void* o, void* o8,
@@ -2377,19 +2341,7 @@ extern "C" int vitmi_attention_fwd_f8(int B, int N, int H, int dh, float scale, 
   if (int rc = attn_check(VITMI_BF16, B, N, H, dh)) return rc;
   VITMI_CHECK_ARG(N <= SEQ_MAX, "attention_fwd_f8: N must be <= %d (the whole-sequence kernel)", SEQ_MAX);
   VITMI_CHECK_ARG(qkv && o && o8 && lse, "attention_fwd_f8: null pointer");
-  VITMI_CHECK_ARG((int64_t)N * 3 * H * DH * 2 < 0x7fffffffLL, "attention_fwd_f8: one batch row block exceeds 2 GiB");
-  const double bh = (double)B * H, fl = 4.0 * bh * N * N * DH, by = bh * N * DH * 2 * (3 + 1 + 2) + bh * N * 4;
-  if (q64()) {
-    hipLaunchKernelGGL((attn_fwd_seq64_bf16<SEQ_MAX, 2>), dim3(B * H), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16*)qkv, (bf16*)o, lse, N, H, scale, (bf16*)o8);
-    VITMI_STAT((attn_fwd_seq64_bf16<SEQ_MAX, 2>), fl, by);
-  } else {
-    hipLaunchKernelGGL((attn_fwd_seq_bf16<SEQ_MAX, 2>), dim3(B * H), dim3(64 * ((N + 31) / 32)), 0,
-                       (hipStream_t)stream, (const bf16*)qkv, (bf16*)o, lse, N, H, scale, (bf16*)o8);
-    VITMI_STAT((attn_fwd_seq_bf16<SEQ_MAX, 2>), fl, by);
-  }
-  VITMI_LAUNCH_CHECK("attention_fwd_f8");
-  return VITMI_OK;
+  return attention_fwd_launch<2>("attention_fwd_f8", VITMI_BF16, B, N, H, scale, qkv, o, o8, lse, (hipStream_t)stream);
 }
 
 #ifdef VITMI_ATTN_STAMPS
@@ -2403,6 +2355,8 @@ extern "C" size_t vitmi_attention_bwd_workspace_size(int B, int N, int H) {
   return (size_t)B * H * N * sizeof(float);
 }
 
+// colsum: the bias-gradient partial rows [B * colsum_rows][3 H dh] (or null); *colsum_rows = how
+// many of them the kernels wrote (0: the caller sums dqkv itself)
 static int attention_bwd_impl(int dtype, int B, int N, int H, int dh, float scale, const void* qkv, const void* o,
                               const void* dout, const float* lse, void* dqkv, void* workspace, size_t ws_bytes,
                               vitmi_stream_t stream, float* colsum, int* colsum_rows) {
@@ -2413,93 +2367,69 @@ static int attention_bwd_impl(int dtype, int B, int N, int H, int dh, float scal
                   "attention_bwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   float* delta = (float*)workspace;
-  const int64_t rows = (int64_t)B * N * H;
-  const int blocks = (int)((rows + 255) / 256);
-  if (dtype == VITMI_BF16 && seq_path(N) && fused_bwd(N)) {
-    switch ((N + 31) / 32) {
-      case 1: launch_fused<1>(B, N, H, scale, qkv, o, dout, lse, delta, dqkv, colsum, s); break;
-      case 2: launch_fused<2>(B, N, H, scale, qkv, o, dout, lse, delta, dqkv, colsum, s); break;
-      case 3: launch_fused<3>(B, N, H, scale, qkv, o, dout, lse, delta, dqkv, colsum, s); break;
-      case 4: launch_fused<4>(B, N, H, scale, qkv, o, dout, lse, delta, dqkv, colsum, s); break;
-      case 5: launch_fused<5>(B, N, H, scale, qkv, o, dout, lse, delta, dqkv, colsum, s); break;
-      case 6: launch_fused<6>(B, N, H, scale, qkv, o, dout, lse, delta, dqkv, colsum, s); break;
-      default: launch_fused<7>(B, N, H, scale, qkv, o, dout, lse, delta, dqkv, colsum, s); break;
+  const AttnPlan p = attn_plan(dtype, N);
+  // algorithmic backward = dP, dQ (dQ kernel) + dV, dK (dK/dV kernel): 8 N^2 dh flops per head, half
+  // of them per kernel (recomputing S is not counted); bytes: q/k/v/o/dO read, dq/dk/dv written (each
+  // kernel of a pair is charged 6 of them), lse read and delta written
+  const double es = dtype == VITMI_BF16 ? 2 : 4, bh = (double)B * H, t = bh * N * DH;
+  const double fl = 4.0 * bh * N * N * DH, by = t * 6 * es + bh * N * 8;
+  const bf16 *q16 = (const bf16*)qkv, *o16 = (const bf16*)o, *do16 = (const bf16*)dout;
+  const float *q32 = (const float*)qkv, *o32 = (const float*)o, *do32 = (const float*)dout;
+  // the whole-sequence bf16 kernels: one workgroup per (batch, head); dK/dV and the single-pass
+  // kernel persistent, one workgroup per CU (its LDS) walking the pairs
+  const int npairs = B * H;
+  const dim3 pairs(npairs), cus(npairs < device_cus() ? npairs : device_cus()), waves(64 * p.nkb);
+  if (p.path == SEQ_BF16 && p.fused) {
+    switch (p.nkb) {   // <= FUSED_NKB
+#define FUSED(NKB)                                                                                             \
+  case NKB:                                                                                                    \
+    launch(attn_bwd_fused_seq_bf16<NKB>, cus, waves, s, 2 * fl, t * 8 * 2 + bh * N * 8, q16, o16, do16, lse, delta, \
+           (bf16*)dqkv, N, H, scale, colsum, npairs);                                                          \
+    break
+      FUSED(1); FUSED(2); FUSED(3); FUSED(4); FUSED(5); FUSED(6); FUSED(7);
+#undef FUSED
     }
-    if (colsum_rows) *colsum_rows = colsum ? B : 0;   // one partial row per batch
-  } else if (dtype == VITMI_BF16 && seq_path(N)) {
+  } else if (p.path == SEQ_BF16) {
     // dQ first: it also writes delta, which the dK/dV kernel consumes
-    const dim3 block(64 * ((N + 31) / 32));
-    {
-      const int npairs = B * H, cus = device_cus();
-      const dim3 gkv(npairs < cus ? npairs : cus);
-      const bool n7 = (N + 31) / 32 == 7;   // N in (192, 224]: the ViT-B/ViT-S shape, N = 197
-      if (n7 && q64())
-        hipLaunchKernelGGL((attn_bwd_dq_seq64_bf16<SEQ_MAX, 7>), dim3(B * H), dim3(256), 0, s, (const bf16*)qkv,
-                           (const bf16*)o, (const bf16*)dout, lse, delta, (bf16*)dqkv, N, H, scale, colsum);
-      else if (n7)
-        hipLaunchKernelGGL((attn_bwd_dq_seq_bf16<SEQ_MAX, 7>), dim3(B * H), block, 0, s, (const bf16*)qkv,
-                           (const bf16*)o, (const bf16*)dout, lse, delta, (bf16*)dqkv, N, H, scale, colsum);
+    if (p.nkb == 7) {   // N in (192, 224]: the ViT-B/ViT-S shape, N = 197
+      if (p.q64)
+        launch(attn_bwd_dq_seq64_bf16<SEQ_MAX, 7>, pairs, dim3(256), s, fl, by, q16, o16, do16, lse, delta, (bf16*)dqkv,
+               N, H, scale, colsum);
       else
-        hipLaunchKernelGGL((attn_bwd_dq_seq_bf16<SEQ_MAX>), dim3(B * H), block, 0, s, (const bf16*)qkv,
-                           (const bf16*)o, (const bf16*)dout, lse, delta, (bf16*)dqkv, N, H, scale, colsum);
-      if (n7)
-        hipLaunchKernelGGL((attn_bwd_dkv_seq_bf16<SEQ_MAX, 7>), gkv, block, 0, s, (const bf16*)qkv, (const bf16*)dout,
-                           lse, (const float*)delta, (bf16*)dqkv, N, H, scale, colsum, npairs);
-      else
-        hipLaunchKernelGGL((attn_bwd_dkv_seq_bf16<SEQ_MAX>), gkv, block, 0, s, (const bf16*)qkv, (const bf16*)dout,
-                           lse, (const float*)delta, (bf16*)dqkv, N, H, scale, colsum, npairs);
-      if (colsum_rows) *colsum_rows = colsum ? B : 0;   // one partial row per batch
+        launch(attn_bwd_dq_seq_bf16<SEQ_MAX, 7>, pairs, waves, s, fl, by, q16, o16, do16, lse, delta, (bf16*)dqkv, N, H,
+               scale, colsum);
+      launch(attn_bwd_dkv_seq_bf16<SEQ_MAX, 7>, cus, waves, s, fl, by, q16, do16, lse, (const float*)delta,
+             (bf16*)dqkv, N, H, scale, colsum, npairs);
+    } else {
+      launch(attn_bwd_dq_seq_bf16<SEQ_MAX>, pairs, waves, s, fl, by, q16, o16, do16, lse, delta, (bf16*)dqkv, N, H,
+             scale, colsum);
+      launch(attn_bwd_dkv_seq_bf16<SEQ_MAX>, cus, waves, s, fl, by, q16, do16, lse, (const float*)delta, (bf16*)dqkv,
+             N, H, scale, colsum, npairs);
     }
-  } else if (dtype == VITMI_BF16) {
+  } else if (p.path == STREAM_BF16) {
     // dQ first: it also writes delta, which the dK/dV kernel consumes
-    dim3 grid((N + 127) / 128, B * H);
-    hipLaunchKernelGGL(attn_bwd_dq_bf16, grid, dim3(256), 0, s, (const bf16*)qkv, (const bf16*)o,
-                       (const bf16*)dout, lse, delta, (bf16*)dqkv, N, H, scale, colsum);
-    hipLaunchKernelGGL(attn_bwd_dkv_bf16, grid, dim3(256), 0, s, (const bf16*)qkv, (const bf16*)dout,
-                       lse, (const float*)delta, (bf16*)dqkv, N, H, scale, colsum);
-    // one bias-gradient partial row per (batch, 128-row block)
-    if (colsum_rows) *colsum_rows = colsum ? B * (int)grid.x : 0;
-  } else if (seq_path(N)) {
+    const dim3 grid((N + 127) / 128, B * H);
+    launch(attn_bwd_dq_bf16, grid, dim3(256), s, fl, by, q16, o16, do16, lse, delta, (bf16*)dqkv, N, H, scale, colsum);
+    launch(attn_bwd_dkv_bf16, grid, dim3(256), s, fl, by, q16, do16, lse, (const float*)delta, (bf16*)dqkv, N, H,
+           scale, colsum);
+  } else if (p.path == SEQ_F32) {
     // dQ first: it also writes delta, which the dK/dV kernel consumes
-    const dim3 block(64 * ((N + 31) / 32));
-    hipLaunchKernelGGL(attn_bwd_dq_seq_f32<SEQ_MAX>, dim3(B * H), block, 0, s, (const float*)qkv, (const float*)o,
-                       (const float*)dout, lse, delta, (float*)dqkv, N, H, scale);
-    hipLaunchKernelGGL(attn_bwd_dkv_seq_f32<SEQ_MAX>, dim3(B * H), block, 0, s, (const float*)qkv,
-                       (const float*)dout, lse, (const float*)delta, (float*)dqkv, N, H, scale);
+    launch(attn_bwd_dq_seq_f32<SEQ_MAX>, pairs, waves, s, fl, by, q32, o32, do32, lse, delta, (float*)dqkv, N, H,
+           scale);
+    launch(attn_bwd_dkv_seq_f32<SEQ_MAX>, pairs, waves, s, fl, by, q32, do32, lse, (const float*)delta, (float*)dqkv,
+           N, H, scale);
   } else {
-    hipLaunchKernelGGL(attn_bwd_delta<float>, dim3(blocks), dim3(256), 0, s, (const float*)o,
-                       (const float*)dout, delta, B * N, N, H);
-    dim3 grid((N + 63) / 64, B * H);
-    hipLaunchKernelGGL(attn_bwd_dkv_f32, grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout,
-                       lse, (const float*)delta, (float*)dqkv, N, H, scale);
-    hipLaunchKernelGGL(attn_bwd_dq_f32, grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout,
-                       lse, (const float*)delta, (float*)dqkv, N, H, scale);
+    // (the streamed fp32 backward records no work)
+    const dim3 grid((N + 63) / 64, B * H);
+    hipLaunchKernelGGL(attn_bwd_delta<float>, dim3((unsigned)(((int64_t)B * N * H + 255) / 256)), dim3(256), 0, s, o32,
+                       do32, delta, B * N, N, H);
+    hipLaunchKernelGGL(attn_bwd_dkv_f32, grid, dim3(256), 0, s, q32, do32, lse, (const float*)delta, (float*)dqkv, N,
+                       H, scale);
+    hipLaunchKernelGGL(attn_bwd_dq_f32, grid, dim3(256), 0, s, q32, do32, lse, (const float*)delta, (float*)dqkv, N,
+                       H, scale);
   }
   VITMI_LAUNCH_CHECK("attention_bwd");
-  {
-    // algorithmic backward = dP, dQ (dQ kernel) + dV, dK (dK/dV kernel): 8 N^2 dh flops per head
-    // (recomputing S is not counted); bytes: q/k/v/o/dO read, dq/dk/dv written, lse/delta
-    const double es = dtype == VITMI_BF16 ? 2 : 4, bh = (double)B * H, t = bh * N * DH;
-    const double fl = 4.0 * bh * N * N * DH;
-    if (dtype == VITMI_BF16 && seq_path(N) && fused_bwd(N)) {
-      // (launch_fused records its own)
-    } else if (dtype == VITMI_BF16 && seq_path(N)) {
-      if ((N + 31) / 32 == 7) {
-        if (q64()) VITMI_STAT((attn_bwd_dq_seq64_bf16<SEQ_MAX, 7>), fl, t * 6 * es + bh * N * 8);
-        else VITMI_STAT((attn_bwd_dq_seq_bf16<SEQ_MAX, 7>), fl, t * 6 * es + bh * N * 8);
-        VITMI_STAT((attn_bwd_dkv_seq_bf16<SEQ_MAX, 7>), fl, t * 6 * es + bh * N * 8);
-      } else {
-        VITMI_STAT(attn_bwd_dq_seq_bf16<SEQ_MAX>, fl, t * 6 * es + bh * N * 8);
-        VITMI_STAT(attn_bwd_dkv_seq_bf16<SEQ_MAX>, fl, t * 6 * es + bh * N * 8);
-      }
-    } else if (dtype == VITMI_BF16) {
-      VITMI_STAT(attn_bwd_dq_bf16, fl, t * 6 * es + bh * N * 8);
-      VITMI_STAT(attn_bwd_dkv_bf16, fl, t * 6 * es + bh * N * 8);
-    } else if (seq_path(N)) {
-      VITMI_STAT(attn_bwd_dq_seq_f32<SEQ_MAX>, fl, t * 6 * es + bh * N * 8);
-      VITMI_STAT(attn_bwd_dkv_seq_f32<SEQ_MAX>, fl, t * 6 * es + bh * N * 8);
-    }
-  }
+  if (colsum_rows && colsum) *colsum_rows = B * p.colsum_rows;
   return VITMI_OK;
 }
 
@@ -2511,12 +2441,15 @@ extern "C" int vitmi_attention_bwd(int dtype, int B, int N, int H, int dh, float
                             nullptr);
 }
 
+// vitmi_attention_bwd_bias's workspace: delta (padded to 256 B), then the partial rows
+static size_t bias_delta_bytes(int B, int N, int H) {
+  return (vitmi_attention_bwd_workspace_size(B, N, H) + 255) / 256 * 256;
+}
+
 extern "C" size_t vitmi_attention_bwd_bias_workspace_size(int B, int N, int H) {
-  const size_t delta = ((size_t)B * H * N * sizeof(float) + 255) / 256 * 256;
-  // fused partial rows: one per batch (whole-sequence kernels) or per (batch, 128-row block)
-  const size_t part = (size_t)B * ((N + 127) / 128) * 3 * H * DH * sizeof(float);
+  const size_t part = (size_t)B * attn_colsum_rows_max(N) * 3 * H * DH * sizeof(float);
   const size_t fallback = vitmi_bias_grad_workspace_size((int64_t)B * N, 3LL * H * DH);
-  return delta + (part > fallback ? part : fallback);
+  return bias_delta_bytes(B, N, H) + (part > fallback ? part : fallback);
 }
 
 extern "C" int vitmi_attention_bwd_bias(int dtype, int B, int N, int H, int dh, float scale, const void* qkv,
@@ -2525,7 +2458,7 @@ extern "C" int vitmi_attention_bwd_bias(int dtype, int B, int N, int H, int dh, 
   VITMI_CHECK_ARG(dbias != nullptr, "attention_bwd_bias: dbias is null");
   VITMI_CHECK_ARG(workspace && ws_bytes >= vitmi_attention_bwd_bias_workspace_size(B, N, H),
                   "attention_bwd_bias: workspace too small");
-  const size_t delta = ((size_t)B * H * N * sizeof(float) + 255) / 256 * 256;
+  const size_t delta = bias_delta_bytes(B, N, H);
   float* part = (float*)((char*)workspace + delta);
   int rows = 0;
   if (int rc = attention_bwd_impl(dtype, B, N, H, dh, scale, qkv, o, dout, lse, dqkv, workspace, delta,

@@ -101,13 +101,9 @@ __global__ void conv_col2im_kernel(ConvGeo g, const T* __restrict__ dp, int Kp, 
 }
 
 // ---------------------------------------------------------------- depthwise 3x3 + BatchNorm
-// VITMI_DW_ROWS (default 1): the stats / dz / dx passes walk image rows with the 3x3 window in
-// registers (the *_rows kernels); 0: one pixel per thread-iteration, 9 tap loads each
-#ifndef VITMI_DW_ROWS
-#define VITMI_DW_ROWS 1
-#endif
-// Thread (pixel lane pl, channel group cg) with cg = tid % C4 fixed for the whole grid-stride
-// loop: 256 / C4 pixels per block iteration (C4 divides 256).  Pixel indices are 32-bit
+// The stats / dz / dx passes walk image rows with the 3x3 window in registers (the *_rows kernels).
+// The other passes: thread (pixel lane pl, channel group cg) with cg = tid % C4 fixed for the whole
+// grid-stride loop: 256 / C4 pixels per block iteration (C4 divides 256).  Pixel indices are 32-bit
 // (n = B*H*W < 2^31, checked on the host): one (b, h, w) split per pixel, none per tap.
 struct DwGeo {
   int B, H, W, C;
@@ -127,55 +123,9 @@ __device__ __forceinline__ void dw_split(const DwGeo& g, uint32_t p, uint32_t& b
 __device__ __forceinline__ int64_t img_row0(uint32_t b, int64_t img, int64_t off) { return (int64_t)b * img + off; }
 
 // z = dwconv3x3(x) (same padding) -> z scratch; per-block partial sum / sum of squares.
-__global__ __launch_bounds__(256) void dw_fwd_stats_kernel(DwGeo g, const float* __restrict__ x,
-                                                           const float* __restrict__ wt,  // [3][3][C]
-                                                           float* __restrict__ z, float* __restrict__ part) {
-  __shared__ f32x4 red[2][256];
-  const int C4 = g.C / 4, cg = threadIdx.x % C4, lanes = 256 / C4, pl = threadIdx.x / C4;
-  const int c = cg * 4;
-  const uint32_t n = (uint32_t)g.B * g.H * g.W;
-  f32x4 wv[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) wv[k] = *(const f32x4*)(wt + k * g.C + c);
-  f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-  for (uint32_t p = blockIdx.x * lanes + pl; p < n; p += gridDim.x * lanes) {
-    uint32_t b;
-    int h, w;
-    dw_split(g, p, b, h, w);
-    const float* xb = x + img_row0(b, g.x_img, g.x_off) * g.ldx + c;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int hh = h + i - 1;
-      if (hh < 0 || hh >= g.H) continue;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int ww = w + j - 1;
-        if (ww < 0 || ww >= g.W) continue;
-        acc += wv[i * 3 + j] * *(const f32x4*)(xb + (int64_t)(hh * g.W + ww) * g.ldx);
-      }
-    }
-    *(f32x4*)(z + (int64_t)p * g.ldz + c) = acc;
-    s1 += acc;
-    s2 += acc * acc;
-  }
-  red[0][threadIdx.x] = s1;
-  red[1][threadIdx.x] = s2;
-  __syncthreads();
-  if (pl == 0) {
-    for (int l = 1; l < lanes; ++l) {
-      s1 += red[0][l * C4 + cg];
-      s2 += red[1][l * C4 + cg];
-    }
-    *(f32x4*)(part + (int64_t)blockIdx.x * 2 * g.C + c) = s1;
-    *(f32x4*)(part + (int64_t)blockIdx.x * 2 * g.C + g.C + c) = s2;
-  }
-}
-
-// The same pass walking image rows: thread (row b*H + h, channel group cg) runs along w with the
-// 3x3 window in registers (3 new taps per pixel instead of 9, no per-pixel index divisions).
-// Taps are summed in the same (i, j) order as dw_fwd_stats_kernel (out-of-image taps add 0), so z
-// is identical; the per-block statistics partials follow this kernel's own fixed order.
+// Walks image rows: thread (row b*H + h, channel group cg) runs along w with the 3x3 window in
+// registers (3 new taps per pixel instead of 9, no per-pixel index divisions).  Taps are summed in
+// (i, j) order (out-of-image taps add 0); the per-block statistics partials follow a fixed order.
 __global__ __launch_bounds__(256) void dw_fwd_stats_rows_kernel(DwGeo g, const float* __restrict__ x,
                                                                 const float* __restrict__ wt,  // [3][3][C]
                                                                 float* __restrict__ z, float* __restrict__ part) {
@@ -365,65 +315,8 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __re
 
 // dz = gamma * rstd * (dy - k1 - zhat * k2) -> scratch; per-block partials of
 // dW[i][j][c] = sum_p dz[p][c] * x[p + (i-1, j-1)][c].
-template <typename TD>
-__global__ __launch_bounds__(256) void dw_bwd_dz_kernel(DwGeo g, const TD* __restrict__ dy, int64_t lddy,
-                                                        int64_t dy_img, int64_t dy_off,
-                                                        const float* __restrict__ z, const float* __restrict__ x,
-                                                        const float* __restrict__ mean,
-                                                        const float* __restrict__ rstd,
-                                                        const float* __restrict__ gamma,
-                                                        const float* __restrict__ kk, float* __restrict__ dz,
-                                                        float* __restrict__ part) {
-  __shared__ f32x4 red[256];
-  const int C4 = g.C / 4, cg = threadIdx.x % C4, lanes = 256 / C4, pl = threadIdx.x / C4;
-  const int c = cg * 4;
-  const uint32_t n = (uint32_t)g.B * g.H * g.W;
-  const f32x4 mu = *(const f32x4*)(mean + c), rs = *(const f32x4*)(rstd + c);
-  const f32x4 gr = *(const f32x4*)(gamma + c) * rs;
-  const f32x4 k1 = *(const f32x4*)(kk + c), k2 = *(const f32x4*)(kk + g.C + c);
-  f32x4 dw[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) dw[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (uint32_t p = blockIdx.x * lanes + pl; p < n; p += gridDim.x * lanes) {
-    uint32_t b;
-    int h, w;
-    dw_split(g, p, b, h, w);
-    const int hw_i = h * g.W + w;
-    const TD* src = dy + (img_row0(b, dy_img, dy_off) + hw_i) * lddy + c;
-    f32x4 d;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) d[e] = to_f32(src[e]);
-    const f32x4 zh = (*(const f32x4*)(z + (int64_t)p * g.ldz + c) - mu) * rs;
-    const f32x4 dzv = gr * (d - k1 - zh * k2);
-    *(f32x4*)(dz + (int64_t)p * g.ldz + c) = dzv;
-    const float* xb = x + img_row0(b, g.x_img, g.x_off) * g.ldx + c;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int hh = h + i - 1;
-      if (hh < 0 || hh >= g.H) continue;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int ww = w + j - 1;
-        if (ww < 0 || ww >= g.W) continue;
-        dw[i * 3 + j] += dzv * *(const f32x4*)(xb + (int64_t)(hh * g.W + ww) * g.ldx);
-      }
-    }
-  }
-  for (int k = 0; k < 9; ++k) {
-    __syncthreads();
-    red[threadIdx.x] = dw[k];
-    __syncthreads();
-    if (pl == 0) {
-      f32x4 s = dw[k];
-      for (int l = 1; l < lanes; ++l) s += red[l * C4 + cg];
-      *(f32x4*)(part + ((int64_t)blockIdx.x * 9 + k) * g.C + c) = s;
-    }
-  }
-}
-
-// The same pass walking image rows (see dw_fwd_stats_rows_kernel): the x window slides along w,
-// so each pixel loads dy, z and 3 new x taps.  dz is identical; the weight-gradient partials
-// follow this kernel's fixed order.
+// Walks image rows (see dw_fwd_stats_rows_kernel): the x window slides along w, so each pixel loads
+// dy, z and 3 new x taps; the weight-gradient partials follow a fixed order.
 template <typename TD>
 __global__ __launch_bounds__(256) void dw_bwd_dz_rows_kernel(DwGeo g, const TD* __restrict__ dy, int64_t lddy,
                                                              int64_t dy_img, int64_t dy_off,
@@ -500,8 +393,8 @@ __global__ __launch_bounds__(256) void dw_bwd_dz_rows_kernel(DwGeo g, const TD* 
 }
 
 // dx[p] += sum_{i,j} w[i][j] * dz[p - (i-1, j-1)] walking image rows: thread (row, channel group)
-// slides a 3x3 dz window along w (3 new loads per pixel); same (i, j) order as dw_bwd_dx_kernel,
-// so dx is identical.
+// slides a 3x3 dz window along w (3 new loads per pixel), taps summed in (i, j) order
+// (rows of dx like x's).
 __global__ __launch_bounds__(256) void dw_bwd_dx_rows_kernel(DwGeo g, const float* __restrict__ dz,
                                                              const float* __restrict__ wt, float* __restrict__ dx) {
   const uint32_t C4 = g.C / 4;
@@ -561,35 +454,6 @@ __global__ __launch_bounds__(1024) void dw_wgrad_finalize_kernel(const float* __
   const bool ok = e < 9 * C;
   const double s = block_colsum(part, G, 9 * C, e, ok, red);
   if (threadIdx.x < RED_COLS && ok) dwt[e] += (float)s;
-}
-
-// dx[p] += sum_{i,j} w[i][j] * dz[p - (i-1, j-1)]   (rows of dx like x's)
-__global__ void dw_bwd_dx_kernel(DwGeo g, const float* __restrict__ dz, const float* __restrict__ wt,
-                                 float* __restrict__ dx) {
-  const uint32_t C4 = g.C / 4;
-  const uint32_t total = (uint32_t)g.B * g.H * g.W * C4;
-  for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
-    const int c = (int)(t % C4) * 4;
-    const uint32_t p = t / C4;
-    uint32_t b;
-    int h, w;
-    dw_split(g, p, b, h, w);
-    const float* zb = dz + ((int64_t)p - (h * g.W + w)) * g.ldz + c;   // (b, 0, 0)
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int hh = h - i + 1;
-      if (hh < 0 || hh >= g.H) continue;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int ww = w - j + 1;
-        if (ww < 0 || ww >= g.W) continue;
-        acc += *(const f32x4*)(wt + (i * 3 + j) * g.C + c) * *(const f32x4*)(zb + (int64_t)(hh * g.W + ww) * g.ldz);
-      }
-    }
-    float* d = dx + (img_row0(b, g.x_img, g.x_off) + h * g.W + w) * g.ldx + c;
-    *(f32x4*)d = *(const f32x4*)d + acc;
-  }
 }
 
 static unsigned grid_of(int64_t work, int per_block = 256, int cap = 4096) {
@@ -715,16 +579,11 @@ extern "C" int vitmi_dwconv_bn_fwd(int B, int H, int W, int C, const float* x, i
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = (int64_t)B * H * W;
   float* part = (float*)workspace;
-#if VITMI_DW_ROWS
   // row-walking stats pass: one thread per (image row, channel group), at most dw_blocks blocks
   // (the workspace's partial rows)
   int G = (int)(((int64_t)B * H * (C / 4) + 255) / 256);
   if (G > dw_blocks(n, C)) G = dw_blocks(n, C);
   hipLaunchKernelGGL(dw_fwd_stats_rows_kernel, dim3(G), dim3(256), 0, st, g, x, wt, z, part);
-#else
-  const int G = dw_blocks(n, C);
-  hipLaunchKernelGGL(dw_fwd_stats_kernel, dim3(G), dim3(256), 0, st, g, x, wt, z, part);
-#endif
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + RED_COLS - 1) / RED_COLS), dim3(1024), 0, st, (const float*)part, G, C, n, eps,
                      momentum, mean, rstd, run_mean, run_var, training);
   const int64_t work = n * (C / 4);
@@ -763,7 +622,6 @@ extern "C" int vitmi_dwconv_bn_bwd(int B, int H, int W, int C, const void* dy, i
   }
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + RED_COLS - 1) / RED_COLS), dim3(1024), 0, st, (const float*)part, G, C, n,
                      dgamma, dbeta, kk);
-#if VITMI_DW_ROWS
   int Gw = (int)(((int64_t)B * H * (C / 4) + 255) / 256);
   if (Gw > G) Gw = G;
   if (dy_dtype == VITMI_BF16)
@@ -776,17 +634,6 @@ extern "C" int vitmi_dwconv_bn_bwd(int B, int H, int W, int C, const void* dy, i
                      dwt);
   hipLaunchKernelGGL(dw_bwd_dx_rows_kernel, dim3(grid_of((int64_t)B * H * (C / 4))), dim3(256), 0, st, g, (const float*)dz,
                      wt, dx);
-#else
-  if (dy_dtype == VITMI_BF16)
-    hipLaunchKernelGGL(dw_bwd_dz_kernel<bf16>, dim3(G), dim3(256), 0, st, g, (const bf16*)dy, lddy, dy_img, dy_off, z,
-                       x, mean, rstd, gamma, (const float*)kk, dz, part);
-  else
-    hipLaunchKernelGGL(dw_bwd_dz_kernel<float>, dim3(G), dim3(256), 0, st, g, (const float*)dy, lddy, dy_img, dy_off,
-                       z, x, mean, rstd, gamma, (const float*)kk, dz, part);
-  hipLaunchKernelGGL(dw_wgrad_finalize_kernel, dim3((9 * C + RED_COLS - 1) / RED_COLS), dim3(1024), 0, st, (const float*)part, G, C,
-                     dwt);
-  hipLaunchKernelGGL(dw_bwd_dx_kernel, dim3(grid_of(n * (C / 4))), dim3(256), 0, st, g, (const float*)dz, wt, dx);
-#endif
   VITMI_LAUNCH_CHECK("dwconv_bn_bwd");
   return VITMI_OK;
 }

@@ -172,9 +172,6 @@ struct FoldBatch {
   FoldJob j[FOLD_MAX];
 };
 
-#ifndef VITMI_FOLD_UNROLL
-#define VITMI_FOLD_UNROLL 8
-#endif
 __global__ __launch_bounds__(1024) void fold_kernel(FoldBatch b) {
   __shared__ float red[64][17];
   const FoldJob J = b.j[blockIdx.y];
@@ -183,7 +180,7 @@ __global__ __launch_bounds__(1024) void fold_kernel(FoldBatch b) {
   const int64_t col = (int64_t)blockIdx.x * 16 + c;
   float a = 0.f;
   if (col < J.cols) {
-#pragma unroll VITMI_FOLD_UNROLL
+#pragma unroll 8
     for (int64_t r = gi; r < J.rows; r += 64) a += J.part[r * J.ld + col];
   }
   red[gi][c] = a;

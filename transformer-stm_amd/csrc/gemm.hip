@@ -26,32 +26,13 @@
 // store reads the stale soffset and lands on another row group (seen on the GELU-dropout and
 // residual epilogues).
 #define VMEM_SGPR_GUARD "s_nop 4\n\t"
-// cache-policy modifiers of the epilogue's output stores (empty: the default policy)
-// (VITMI_ST_MASK bits: 1 = gelu' aux, 2 = bf16 C, 4 = fp32 C / residual output, 8 = split-K
-// partial slabs; the bit's stores carry the non-temporal hint)
-#ifndef VITMI_ST_MASK
-#define VITMI_ST_MASK 3
-#endif
-#if VITMI_ST_MASK & 1
+// cache-policy modifiers of the epilogue's output stores, pasted into their asm text (empty: the
+// default policy): the gelu' aux and bf16 C stores carry the non-temporal hint, the fp32 C /
+// residual output and the split-K partial slabs do not
 #define VITMI_ST_AUX " nt"
-#else
-#define VITMI_ST_AUX ""
-#endif
-#if VITMI_ST_MASK & 2
 #define VITMI_ST_C16 " nt"
-#else
-#define VITMI_ST_C16 ""
-#endif
-#if VITMI_ST_MASK & 4
-#define VITMI_ST_C32 " nt"
-#else
 #define VITMI_ST_C32 ""
-#endif
-#if VITMI_ST_MASK & 8
-#define VITMI_ST_PART " nt"
-#else
 #define VITMI_ST_PART ""
-#endif
 
 namespace vitmi {
 
@@ -133,31 +114,21 @@ __device__ __forceinline__ int64_t aux_at(const GemmArgs& g, int64_t row, int64_
   return tile * 65536 + (((wave * 8 + mi) * 2 + (ni >> 1)) * 1024 + lane * 16 + (ni & 1) * 8) / 2 + (c & 3);
 }
 
-// (tile-row, tile-col) of tile index tl: row-major over the tiles_n tile columns (a persistent
-// block walks consecutive tiles, so an XCD's concurrent tiles share A row panels in its L2;
-// grouped column-major orders measured 0.5-1 % slower end to end)
-// row panels per tile group (0: row-major tiles).  C3 step 7292-7314 -> 7335-7350 img/s over
-// three rounds (GM 5 and 7 as row-major; fc1 + GELU 308-313 -> 299-304 µs, DGELU 297-302 -> 288;
+// (tile-row, tile-col) of tile index tl: groups of TILE_GM row panels walked column by column (a
+// persistent block walks consecutive tiles): an XCD's 32 concurrent tiles span TILE_GM row panels
+// x 32/TILE_GM column panels instead of ~3 x all of them as in row-major order, and the next ones
+// reuse the same row panels from its L2.  C3 step 7292-7314 (row-major) -> 7335-7350 img/s over
+// three rounds (5 and 7 as row-major; fc1 + GELU 308-313 -> 299-304 µs, DGELU 297-302 -> 288;
 // profiles/r06_gm*)
-#ifndef VITMI_TILE_GM
-#define VITMI_TILE_GM 6
-#endif
+static constexpr int TILE_GM = 6;
 __device__ __forceinline__ void tile_rc(const GemmArgs& g, int tl, int& tm, int& tn) {
-  if constexpr (VITMI_TILE_GM > 1) {
-    // groups of GM row panels walked column by column: an XCD's 32 concurrent tiles span GM row
-    // panels x 32/GM column panels instead of ~3 x all of them, and the next ones reuse the
-    // same GM row panels from its L2
-    const int tiles_m = (int)((g.M + 255) >> 8);
-    const int per = VITMI_TILE_GM * g.tiles_n;
-    const int grp = tl / per, r = tl - grp * per;
-    const int m0 = grp * VITMI_TILE_GM;
-    const int gm = tiles_m - m0 < VITMI_TILE_GM ? tiles_m - m0 : VITMI_TILE_GM;
-    tn = r / gm;
-    tm = m0 + (r - tn * gm);
-  } else {
-    tm = tl / g.tiles_n;
-    tn = tl - tm * g.tiles_n;
-  }
+  const int tiles_m = (int)((g.M + 255) >> 8);
+  const int per = TILE_GM * g.tiles_n;
+  const int grp = tl / per, r = tl - grp * per;
+  const int m0 = grp * TILE_GM;
+  const int gm = tiles_m - m0 < TILE_GM ? tiles_m - m0 : TILE_GM;
+  tn = r / gm;
+  tm = m0 + (r - tn * gm);
 }
 
 // ---- epilogue descriptors ----------------------------------------------------
@@ -194,7 +165,7 @@ struct Epi {
   template <typename TC>
   static constexpr int vmem_ops = (ces<TC> == 2 ? 16 * ((SPLIT == SPLIT_X3 ? 3 : SPLIT == SPLIT_F8 ? 2 : 1) + second_out) : 32) +
                                   (loads == LD_AUX ? 16 : loads != LD_NONE ? 32 : 0);
-  // gemm256's tail split.  Measured: it pays off for long reductions (>= `mink` = VITMI_TAIL_MINK
+  // gemm256's tail split.  Measured: it pays off for long reductions (>= `mink` = TAIL_MINK
   // K-steps) and at any length for the DGELU epilogue (whose partial units skip its aux loads); a
   // wash or a loss for K = 768 otherwise.  Accumulating epilogues never split (their K-slabs fill the
   // chip), and SPLIT_F8 tiles stay whole: the fix-up kernel does not write the split-f8 rows.
@@ -403,11 +374,7 @@ __device__ __forceinline__ f32x4 mma8(const Frag<bf16>& a0, const Frag<bf16>& a1
                                                                     12, 13, 14, 15));
   const i32x8 b = __builtin_bit_cast(i32x8, __builtin_shufflevector(b0.v, b1.v, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11,
                                                                     12, 13, 14, 15));
-#ifdef VITMI_F6_TIMING   // DIAGNOSTIC: the same bytes read as e2m3 (MX FP6 rate); results meaningless
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 2, 2, 0, F8_E8M0_LO, 0, F8_E8M0_ONE);
-#else
   return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, F8_E8M0_LO, 0, F8_E8M0_ONE);
-#endif
 }
 __device__ __forceinline__ f32x4 mma(const Frag<float>& a, const Frag<float>& b, f32x4 c) {
 #pragma unroll
@@ -618,12 +585,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs g) {
 // Block ids are remapped so consecutive tiles of one XCD share an A row panel.
 // =============================================================================
 // row groups per load batch of the loading epilogues (fp32 residual+accum; DGELU loads all 8)
-#ifndef VITMI_EPI_RB_BF16
-#define VITMI_EPI_RB_BF16 8
-#endif
-#ifndef VITMI_EPI_RB_F32
-#define VITMI_EPI_RB_F32 4
-#endif
+static constexpr int EPI_RB_BF16 = 8, EPI_RB_F32 = 4;
 namespace g256 {
 // raw s_barrier that the compiler may not move memory operations across; DMA (vmcnt)
 // stays in flight (a __syncthreads() would drain it).
@@ -1259,7 +1221,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmArgs g, int nwg) {
         // epilogues that load: RB row groups at a time (all 4 column groups each; 64 VGPRs of
         // loaded operand per wait -- the fragment registers are free here), stored row by row
         // like the store-only epilogues below
-        constexpr int RB = E::loads == LD_AUX ? VITMI_EPI_RB_BF16 : VITMI_EPI_RB_F32;
+        constexpr int RB = E::loads == LD_AUX ? EPI_RB_BF16 : EPI_RB_F32;
         if constexpr (E::loads == LD_AUX) {
           // gelu'(u) arrives as whole 128-B lines too: each lane loads 16 B of one row (8 rows x
           // 128 B per instruction; a C^T-layout load would take 16 rows x 32 B), the wave writes
@@ -1702,17 +1664,12 @@ static int grid256(int nwg, int splits) {
 // Tail split: when the last round of a persistent launch would leave more than half of the
 // blocks idle (ViT N=768 GEMMs: 591 tiles on 256 CUs), its tiles are split into S K-ranges
 // (S <= 4, >= 2 K-steps each) so that round takes ~1/S of the time.
-#ifndef VITMI_TAIL_SMAX
-#define VITMI_TAIL_SMAX 4
-#endif
-#ifndef VITMI_TAIL_MINK
-#define VITMI_TAIL_MINK 16
-#endif
+static constexpr int TAIL_SMAX = 4, TAIL_MINK = 16;
 static bool tail_plan(int nwg, int gx, int nk, int& S, int& ks, int& ntail) {
   ntail = nwg % gx;
   if (nwg < gx || ntail == 0 || 2 * ntail > gx || nk < 4) return false;
   S = gx / ntail;
-  if (S > VITMI_TAIL_SMAX) S = VITMI_TAIL_SMAX;
+  if (S > TAIL_SMAX) S = TAIL_SMAX;
   if (S < 2) return false;
   ks = (nk + S - 1) / S;
   if (ks < 2) ks = 2;
@@ -1760,7 +1717,7 @@ static int launch_t(GemmArgs g, int splits, bool big, hipStream_t s) {
       g.t_full = nwg;
       g.nsplit = 1;
       g.ksplit = 0;
-      if (splits == 1 && E::tail_split && g.k_per_split / 64 >= E::tail_min_ksteps(VITMI_TAIL_MINK) && g.tail_ws &&
+      if (splits == 1 && E::tail_split && g.k_per_split / 64 >= E::tail_min_ksteps(TAIL_MINK) && g.tail_ws &&
           tail_plan(nwg, gx, (int)(g.k_per_split / 64), S, ks, ntail) &&
           g.tail_ws_bytes >= (size_t)ntail * S * 256 * 256 * sizeof(float)) {
         g.t_full = nwg - ntail;

@@ -12,15 +12,11 @@
 
 namespace vitmi {
 
-// Outputs leave with the non-temporal hint, as gemm256's bf16 outputs (VITMI_NT_LN): forward
-// 36.7 -> 34.9 us, backward 126 -> 122 us, step +0.4 % (profiles/r03_store_nt/ln_*)
-#ifndef VITMI_NT_LN
-#define VITMI_NT_LN 1
-#endif
+// Outputs leave with the non-temporal hint, as gemm256's bf16 outputs: forward 36.7 -> 34.9 us,
+// backward 126 -> 122 us, step +0.4 % (profiles/r03_store_nt/ln_*)
 template <typename V>
 __device__ __forceinline__ void put(V* p, V v) {
-  if constexpr (VITMI_NT_LN) __builtin_nontemporal_store(v, p);
-  else *p = v;
+  __builtin_nontemporal_store(v, p);
 }
 template <typename TY>
 __device__ __forceinline__ void store4(TY* p, f32x4 v);
@@ -160,14 +156,10 @@ __global__ __launch_bounds__(256) void ln_fwd_small_kernel(int64_t M, const floa
 }
 
 // ---------------------------------------------------------------- backward
-// VITMI_LN_BWD_NTLD: the backward's once-read inputs (x, dy, dres) with the non-temporal hint
-#ifndef VITMI_LN_BWD_NTLD
-#define VITMI_LN_BWD_NTLD 1
-#endif
+// the backward's once-read inputs (x, dy, dres) with the non-temporal hint
 template <typename V>
 __device__ __forceinline__ V ldg_s(const V* p) {
-  if constexpr (VITMI_LN_BWD_NTLD) return __builtin_nontemporal_load(p);
-  else return *p;
+  return __builtin_nontemporal_load(p);
 }
 template <typename T>
 __device__ __forceinline__ f32x4 load4s(const T* p);
@@ -315,12 +307,10 @@ __global__ __launch_bounds__(256) void ln_bwd_small_kernel(
   }
 }
 
-#ifndef VITMI_LN_BWD_BLOCKS
-#define VITMI_LN_BWD_BLOCKS 512
-#endif
+static constexpr int LN_BWD_BLOCKS = 512;
 static int ln_blocks_bwd(int64_t M) {
   int64_t g = (M + 3) / 4;
-  return (int)(g < VITMI_LN_BWD_BLOCKS ? (g < 1 ? 1 : g) : VITMI_LN_BWD_BLOCKS);
+  return (int)(g < LN_BWD_BLOCKS ? (g < 1 ? 1 : g) : LN_BWD_BLOCKS);
 }
 
 template <int NV>
@@ -399,10 +389,7 @@ extern "C" int vitmi_layernorm_fwd(int64_t M, int D, const float* x, int64_t ldx
   if (M == 0) return VITMI_OK;
   VITMI_CHECK_ARG(x && gamma && beta && y && mean && rstd, "layernorm_fwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
-#ifndef VITMI_LN_FWD_SMALL
-#define VITMI_LN_FWD_SMALL 1
-#endif
-  if (VITMI_LN_FWD_SMALL && (D == 64 || D == 128) && y_dtype != VITMI_BF16X3 && y_dtype != VITMI_BF16F8 &&
+  if ((D == 64 || D == 128) && y_dtype != VITMI_BF16X3 && y_dtype != VITMI_BF16F8 &&
       y_dtype != VITMI_BF16F8W) {
     const int rw = 64 / (D / 4);
     const dim3 grid((unsigned)((M + 4 * rw - 1) / (4 * rw)));
@@ -455,10 +442,7 @@ extern "C" int vitmi_layernorm_bwd(int64_t M, int D, const void* dy, int dy_dtyp
   const int G = ln_blocks_bwd(M);
   float* part = (float*)workspace;
   const int nv = (D + 255) / 256;
-#ifndef VITMI_LN_BWD_SMALL
-#define VITMI_LN_BWD_SMALL 1
-#endif
-  if (VITMI_LN_BWD_SMALL && (D == 64 || D == 128)) {
+  if (D == 64 || D == 128) {
 #define LNS(LL, TD, LPB)                                                                          \
   hipLaunchKernelGGL((ln_bwd_small_kernel<LL, TD, LPB>), dim3(G), dim3(256), 0, s, M, (const TD*)dy, lddy, x, ldx, \
                      mean, rstd, gamma, dres, ldres, dx, lddx, (bf16*)dx_lp, lddx_lp, part)

@@ -32,20 +32,16 @@ __device__ __forceinline__ void adam1(const AdamArgs& a, float& p, float g, floa
   p = __fsub_rn(p, __fdiv_rn(__fmul_rn(m, a.alpha), den));
 }
 
-// VITMI_ADAM_NT: streaming (non-temporal) loads and stores, two 16-B groups per thread in flight:
-// 573-595 -> 504-526 us per ViT-B step (tools/ln_bench.py, same box; gpurun_out r04_ln A/B)
-#ifndef VITMI_ADAM_NT
-#define VITMI_ADAM_NT 1
-#endif
+// streaming (non-temporal) loads and stores, ADAM_U = two 16-B groups per thread in flight:
+// 573-595 -> 504-526 us per ViT-B step (tools/ln_bench.py, same box, A/B)
+static constexpr int ADAM_U = 2;
 template <typename V>
 __device__ __forceinline__ V ld_s(const V* q) {
-  if constexpr (VITMI_ADAM_NT) return __builtin_nontemporal_load(q);
-  else return *q;
+  return __builtin_nontemporal_load(q);
 }
 template <typename V>
 __device__ __forceinline__ void st_s(V* q, V x) {
-  if constexpr (VITMI_ADAM_NT) __builtin_nontemporal_store(x, q);
-  else *q = x;
+  __builtin_nontemporal_store(x, q);
 }
 
 template <bool LP>
@@ -54,7 +50,7 @@ __global__ __launch_bounds__(256) void adam_kernel(int64_t n, float* __restrict_
                                                    bf16* __restrict__ lp, AdamArgs a) {
   const int64_t n4 = n / 4;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  constexpr int U = VITMI_ADAM_NT ? 2 : 1;
+  constexpr int U = ADAM_U;
   for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += U * stride) {
     f32x4 pv[U], gv[U], mv[U], vv[U];
 #pragma unroll
@@ -239,7 +235,7 @@ __global__ __launch_bounds__(256) void adam_ctl_kernel(int64_t n, float* __restr
     }
     return;
   }
-  constexpr int U = VITMI_ADAM_NT ? 2 : 1;
+  constexpr int U = ADAM_U;
   for (int64_t i0 = first; i0 < n4; i0 += U * stride) {
     f32x4 pv[U], gv[U], mv[U], vv[U];
     bool dec[U];
