@@ -352,6 +352,62 @@ int vitmi_droppath_apply(int64_t M, int64_t N, const float* x, int64_t ldx, void
                          uint32_t drop_thresh, float drop_scale, vitmi_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * LayerScale (CaiT; DeiT-III, BEiT, DINOv2; timm's init_values= with parameters blocks.i.ls1.gamma /
+ * ls2.gamma): a learned per-channel scale gamma (fp32 [N]) on each residual branch,
+ *   x + f[b] * (keep * s * (gamma o (a W^T + b)))        (a: the GEMM input; W [N][K], b [N]),
+ * the element dropout keep * s and the drop-path sample factor f[b] exactly as without it.  Because
+ * gamma o (a W^T + b) = a (gamma o W)^T + gamma o b, the scale is folded into the weight OPERAND of the
+ * branch's last GEMM (out-projection, fc2): W_eff = gamma o W (row n of W times gamma[n]), b_eff = gamma
+ * o b, and every GEMM entry point above runs unchanged on (W_eff, b_eff).  It is part of the model: the
+ * same in training, evaluation and without gradients.
+ *
+ * Backward of one scaled linear, g the gradient entering the branch as the existing code forms it:
+ *   da = g W_eff (the dgrad GEMM on the W_eff operand);  dW_eff = g^T a, db_eff = colsum(g) (the wgrad
+ *   GEMM and the bias column sums, unchanged);  dW = gamma o dW_eff,  db = gamma o db_eff,
+ *   dgamma[n] = sum_k dW_eff[n][k] * W[n][k] + db_eff[n] * b[n]       (W, b: the fp32 masters).
+ * Nothing divides by gamma: a channel with gamma == 0 has a correct, generally nonzero dgamma.
+ *
+ * All four calls: fp32 masters, 16-byte accesses, no atomics, every sum in an order fixed by the shape
+ * alone (bitwise reproducible).  K is a positive multiple of 8, N >= 1, N and K < 2^31 (the fold: N * K /
+ * 8 < 2^31); w, w_eff, dw 16-byte aligned.  The k-major rule of the GEMM that consumes W_eff (K % 64 for
+ * bf16, K % 32 for fp32) is that GEMM's to refuse.
+ *
+ * vitmi_layerscale_fold: w_eff[n][k] = round_to(w_dtype, fl32(gamma[n] * w[n][k])), w_dtype VITMI_F32 or
+ *   VITMI_BF16: one fp32 multiply, one round-to-nearest-even.  bias_eff[n] = fl32(gamma[n] * bias[n]); bias
+ *   and bias_eff are both given or both NULL.  One streaming pass (8 B or 6 B per element).
+ *
+ * vitmi_layerscale_bwd, in place on the gradient destinations: dw holds dW_eff and db holds db_eff.
+ *   dgamma[n] += rowdot(dw[n], w[n]) + db[n] * bias[n];  then, with scale_grads = 1, dw[n][:] *= gamma[n]
+ *   and db[n] *= gamma[n].  One pass over dw (each element is read once, used for the dot and written back
+ *   scaled).  scale_grads = 0 leaves dw and db untouched (a frozen weight whose dW_eff lives in a
+ *   temporary); dgamma NULL skips the reduction (frozen gamma; w and bias are then not read); both: no
+ *   launch.  dw NULL (with dgamma NULL): only db is scaled; db NULL: a linear without bias.
+ *   One wave per row for K <= 1024, one 256-thread block per row above.
+ *   The call relies on dw / db holding exactly this backward's dW_eff / db_eff.  The Python layer
+ *   guarantees it: a gradient destination (vitmi/grads.py GradSink) is either the parameter's ParamArena
+ *   view, zeroed by begin_step at the forward and handed out once (ParamArena.take), or a buffer zeroed
+ *   for this backward; the kernels of this one backward alone add into it before it is returned.  The
+ *   caller orders the call after those kernels, the deferred bias-gradient folds included
+ *   (vitmi_fold_end), and before the gradients leave.
+ *
+ * The standalone module (vitmi.LayerScale, for user-composed blocks, the counterpart of vitmi.DropPath):
+ * vitmi_layerscale_apply: y[M][ldy] (f32 or bf16) = x[M][ldx] (f32) * gamma[col]: the forward, and dx from
+ *   dy.  N % 4 == 0; alignment and leading-dimension rules of vitmi_dropout_apply; gamma 16-byte aligned.
+ * vitmi_layerscale_dgamma: dgamma[col] += sum_m dy[m][col] * x[m][col], in two steps like vitmi_bias_grad:
+ *   per-chunk partial rows in the workspace (vitmi_layerscale_dgamma_workspace_size bytes, 16-byte
+ *   aligned), then the fixed-order fold (queued between vitmi_fold_begin and vitmi_fold_end).  N % 4 == 0,
+ *   leading dims multiples of 4, dy and x 16-byte aligned. */
+int vitmi_layerscale_fold(int64_t N, int64_t K, const float* w, const float* gamma, const float* bias,
+                          void* w_eff, int w_dtype, float* bias_eff, vitmi_stream_t stream);
+int vitmi_layerscale_bwd(int64_t N, int64_t K, const float* w, const float* bias, const float* gamma,
+                         float* dw, float* db, float* dgamma, int scale_grads, vitmi_stream_t stream);
+int vitmi_layerscale_apply(int64_t M, int64_t N, const float* x, int64_t ldx, const float* gamma, void* y,
+                           int y_dtype, int64_t ldy, vitmi_stream_t stream);
+size_t vitmi_layerscale_dgamma_workspace_size(int64_t M, int64_t N);
+int vitmi_layerscale_dgamma(int64_t M, int64_t N, const float* dy, int64_t lddy, const float* x, int64_t ldx,
+                            float* dgamma, void* workspace, size_t ws_bytes, vitmi_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Patch dropout (timm's patch_drop_rate, FLIP, the MAE encoder's random masking): in training each
  * sample keeps K of its np patch tokens and the class token; every block then runs on K + 1 tokens.
  *

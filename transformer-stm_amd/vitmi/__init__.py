@@ -22,6 +22,9 @@ def __getattr__(name):
     if name == "DropPath":   # the stochastic-depth module (vitmi.modules), same lazy import
         from .modules import DropPath
         return DropPath
+    if name == "LayerScale":   # the per-channel branch scale (vitmi.modules), likewise
+        from .modules import LayerScale
+        return LayerScale
     if name in ("patch_keep", "PATCH_SITE"):   # patch dropout's subset selection (vitmi.ops) and its hash site
         from . import ops
         return getattr(ops, name)

@@ -72,6 +72,11 @@ SIGNATURES = {
     "vitmi_dropout_apply": (I, [L, L, P, L, P, I, L, U, U, U, F, P]),
     "vitmi_linear_fwd_droppath": (I, [I, L, L, L, P, P, P, P, I, I, P, P, S, U, U, U, F, L, U, U, F, P]),
     "vitmi_droppath_apply": (I, [L, L, P, L, P, I, L, L, U, U, U, F, U, U, F, P]),
+    "vitmi_layerscale_fold": (I, [L, L, P, P, P, P, I, P, P]),
+    "vitmi_layerscale_bwd": (I, [L, L, P, P, P, P, P, P, I, P]),
+    "vitmi_layerscale_apply": (I, [L, L, P, L, P, P, I, L, P]),
+    "vitmi_layerscale_dgamma_workspace_size": (S, [L, L]),
+    "vitmi_layerscale_dgamma": (I, [L, L, P, L, P, L, P, P, S, P]),
     "vitmi_conv_same_geometry": (I, [I, I, I, I, I, P, P, P, P]),
     "vitmi_conv_im2col": (I, [I, I, I, I, I, I, I, I, I, I, I, I, P, L, L, L, P, I, P]),
     "vitmi_conv_col2im": (I, [I, I, I, I, I, I, I, I, I, I, I, I, P, I, P, L, L, L, I, P]),

@@ -22,6 +22,7 @@ tie_norms          True (one norm1 used twice)      False (norm1/norm2)
 from __future__ import annotations
 
 import dataclasses
+import math
 from dataclasses import dataclass
 
 
@@ -68,8 +69,16 @@ class ViTConfig:
     # each sample keeps a hashed subset of ``kept_patches`` of its patch tokens (the class token
     # always) and every block runs on the shortened sequence; nothing is rescaled.  0 = off.
     patch_drop_rate: float = 0.0
+    # LayerScale (CaiT; DeiT-III, BEiT, DINOv2; timm's init_values=): a learned per-channel gamma on
+    # each residual branch, x + gamma1 * attn(norm1(x)) and x + gamma2 * mlp(norm2(x)), parameters
+    # blocks.i.ls1.gamma / ls2.gamma initialised to this value.  Part of the model (the same in train
+    # and eval).  None = off: no such parameters.  Any finite float is a scale, 0.0 included (a
+    # ReZero-style start); timm treats a falsy value as off, vitmi does not.
+    init_values: "float | None" = None
 
     def __post_init__(self):
+        if self.init_values is not None and not math.isfinite(self.init_values):
+            raise ValueError(f"init_values must be a finite float or None (got {self.init_values})")
         if not 0.0 <= self.drop_path_rate < 1.0:   # (also refuses NaN)
             raise ValueError(f"drop_path_rate must be in [0, 1) (got {self.drop_path_rate})")
         if not 0.0 <= self.patch_drop_rate < 1.0:

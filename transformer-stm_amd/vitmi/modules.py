@@ -26,6 +26,7 @@ product is exact fp32 (f32-input MFMA).
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Dict, List, Optional
 
@@ -371,14 +372,66 @@ class _DropPathFn(torch.autograd.Function):
         return _DropPathFn._apply(dy, ctx.args), None, None, None
 
 
+# ======================================================================= layer scale
+class LayerScale(nn.Module):
+    """Learned per-channel scale of a residual branch, ``x + ls(branch(x))`` (CaiT; timm's LayerScale,
+    ``init_values=``): ``y = x * gamma`` over the last dim of an fp32 ``[..., dim]`` tensor, ``gamma``
+    initialised to ``init_values``.  For user-composed blocks, the counterpart of ``DropPath``;
+    ``Block(init_values=...)`` holds two of these as ``ls1`` / ``ls2`` for their parameters and folds the
+    scale into its GEMM weights instead of calling them.  Any finite ``init_values`` is a scale: 0.0 is
+    a ReZero-style start, not "off" (timm treats a falsy value as off)."""
+
+    def __init__(self, dim: int, init_values: float = 1e-5):
+        super().__init__()
+        init_values = float(init_values)
+        if not math.isfinite(init_values):
+            raise ValueError(f"LayerScale init_values must be finite (got {init_values})")
+        self.init_values = init_values
+        self.gamma = nn.Parameter(torch.full((dim,), init_values))
+
+    def forward(self, x: Tensor) -> Tensor:
+        _check_cuda(x)
+        if x.shape[-1] != self.gamma.numel():
+            raise ValueError(f"vitmi LayerScale: last dim {x.shape[-1]} != {self.gamma.numel()}")
+        return _LayerScaleFn.apply(x, self, self.gamma)
+
+    def extra_repr(self) -> str:
+        return f"dim={self.gamma.numel()}, init_values={self.init_values}"
+
+
+class _LayerScaleFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mod, gamma):
+        xs = x.contiguous().float()
+        ctx.save_for_backward(xs)
+        ctx.mod = mod
+        return ops.layerscale_apply(xs.view(-1, xs.shape[-1]), gamma.detach(), F32).view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (xs,) = ctx.saved_tensors
+        mod = ctx.mod
+        gs = _sink(ctx, 2, (mod.gamma,), getattr(mod, "_arena", None))
+        dy2 = dy.contiguous().float().view(-1, dy.shape[-1])
+        dx = ops.layerscale_apply(dy2, mod.gamma.detach(), F32).view(xs.shape) if ctx.needs_input_grad[0] else None
+        if gs.wants(mod.gamma):
+            ops.layerscale_dgamma(dy2, xs.view(-1, xs.shape[-1]), gs(mod.gamma))
+        return (dx, None) + gs.grads((mod.gamma,))
+
+
 # ======================================================================= block
 class Block(nn.Module):
     """Pre-LN transformer block ``x += Attn(LN1(x)); x += MLP(LN2(x))``
     (ConvTransformerBlock.call, models/CvT(Par).py:261-289; Block.forward, MS_CvT.py:325-333).
-    ``tie_norms=True`` reproduces the Keras model's single ``norm1`` used twice (:248,272,278)."""
+    ``tie_norms=True`` reproduces the Keras model's single ``norm1`` used twice (:248,272,278).
+    ``init_values`` (None: off): LayerScale, ``x += ls1.gamma * Attn(LN1(x)); x += ls2.gamma *
+    MLP(LN2(x))`` with both gammas initialised to it (timm's ``init_values=``; any finite float, 0.0
+    included, is a scale).  The gammas are folded into the out-projection's and fc2's weight operands
+    (include/vitmi.h, "LayerScale"); ``ls1`` / ``ls2`` come last in ``parameters()``."""
 
     def __init__(self, dim: int, num_heads: int, mlp_ratio: float = 4.0, qkv_bias: bool = True,
-                 eps: float = 1e-6, attn_scale: str = "head", tie_norms: bool = False, dtype: str = "bf16"):
+                 eps: float = 1e-6, attn_scale: str = "head", tie_norms: bool = False, dtype: str = "bf16",
+                 init_values: Optional[float] = None):
         super().__init__()
         self.norm1 = LayerNorm(dim, eps)
         self.attn = Attention(dim, num_heads, qkv_bias, attn_scale, dtype)
@@ -400,6 +453,9 @@ class Block(nn.Module):
         self.drop_rate = 0.0     # set by VisionTransformer / the caller (Keras default 0.1)
         self.drop_path = 0.0     # stochastic depth of both branches (VisionTransformer: its linspace rate)
         self.drop_seed: Optional[int] = None   # fixed seed (tests); None = drawn per forward
+        # after every other sub-module: the parameter order without LayerScale is a prefix of this one
+        self.ls1 = LayerScale(dim, init_values) if init_values is not None else None
+        self.ls2 = LayerScale(dim, init_values) if init_values is not None else None
 
     @property
     def _norm2(self) -> LayerNorm:
@@ -425,7 +481,10 @@ class _BlockFn(torch.autograd.Function):
     dropout.  Both are fused into the GEMM epilogues; the backward regenerates the masks
     (vitmi_dropout_apply / vitmi_droppath_apply, one pass per branch).  A non-None ``drop`` with both
     rates 0 is a block that drops nothing inside a model that does: plain epilogues, but none of the
-    cross-block bias-gradient shortcuts or gradient handovers."""
+    cross-block bias-gradient shortcuts or gradient handovers.  A block with LayerScale (``blk.ls1``)
+    runs its two RESIDUAL GEMMs on W_eff = gamma o W, b_eff = gamma o b (vitmi_layerscale_fold) and its
+    backward ends with vitmi_layerscale_bwd on each scaled linear; it takes neither ``prev_fc2_bias``
+    nor ``fc2_bias_done``, the handover it keeps."""
 
     @staticmethod
     def forward(ctx, x, blk, prev_fc2_bias, fc2_bias_done, drop, handover, *params):
@@ -436,14 +495,27 @@ class _BlockFn(torch.autograd.Function):
         x2 = x.contiguous().float().view(M, D)
         n1, n2 = blk.norm1, blk._norm2
         a_ = blk.attn
-        wq, wo = _lp(blk, a_.qkv.weight, T), _lp(blk, a_.proj.weight, T)
-        w1, w2 = _lp(blk, blk.mlp.fc1.weight, T), _lp(blk, blk.mlp.fc2.weight, T)
+        knob = blk.dtype in ("bf16x3", "bf16f8")
+        ls = blk.ls1 is not None
+        wq, wo = _lp(blk, a_.qkv.weight, T), None if ls else _lp(blk, a_.proj.weight, T)
+        w1, w2 = _lp(blk, blk.mlp.fc1.weight, T), None if ls else _lp(blk, blk.mlp.fc2.weight, T)
+        bo, b2 = a_.proj.bias, blk.mlp.fc2.bias
+        if ls:
+            # LayerScale: the two RESIDUAL GEMMs (and the dgrads of the backward) take W_eff = gamma o W
+            # and b_eff = gamma o b, folded from the fp32 masters (not the arena's bf16 shadow, which
+            # holds the unscaled W).  The precision knobs split an fp32 W_eff.
+            if fc2_bias_done or prev_fc2_bias is not None:
+                raise RuntimeError("vitmi: a LayerScale block takes no cross-block fc2 bias-gradient shortcut")
+            wo, bo = ops.layerscale_fold(a_.proj.weight.detach(), blk.ls1.gamma.detach(), bo.detach(),
+                                         F32 if knob else T)
+            w2, b2 = ops.layerscale_fold(blk.mlp.fc2.weight.detach(), blk.ls2.gamma.detach(), b2.detach(),
+                                         F32 if knob else T)
         ctx.blk, ctx.shape = blk, (B, N, D)
         ctx.prev_bias, ctx.bias_done, ctx.drop = prev_fc2_bias, fc2_bias_done, drop
         ctx.handover = handover
         ctx.aux_tiled = T != F32
-        if blk.dtype in ("bf16x3", "bf16f8"):
-            out = _BlockFn._forward_x3(ctx, x2, blk, B, N, D, H, drop, (wq, wo, w1, w2))
+        if knob:
+            out = _BlockFn._forward_x3(ctx, x2, blk, B, N, D, H, drop, (wq, wo, w1, w2), bo, b2)
             return out.view(B, N, D)
         h1, m1, r1 = ops.layernorm_fwd(x2, n1.weight, n1.bias, blk.eps, T)
         qkv = ops.linear_fwd(h1, wq, a_.qkv.bias, T)
@@ -455,17 +527,16 @@ class _BlockFn(torch.autograd.Function):
                 dr = [(seed, site0 + j, rate) for j in range(3)]
             if prate > 0:   # a sample is its N rows
                 dp = [(seed, psite0 + j, prate, N) for j in range(2)]
-        x1 = ops.linear_fwd(o, wo, a_.proj.bias, F32, ops.EPI_RESIDUAL, residual=x2, dropout=dr[0], droppath=dp[0])
+        x1 = ops.linear_fwd(o, wo, bo, F32, ops.EPI_RESIDUAL, residual=x2, dropout=dr[0], droppath=dp[0])
         h2, m2, r2 = ops.layernorm_fwd(x1, n2.weight, n2.bias, blk.eps, T)
         # gelu' stays in the tile-native layout between fc1's epilogue and fc2's dgrad (bf16)
         act, u = ops.linear_fwd(h2, w1, blk.mlp.fc1.bias, T, ops.EPI_BIAS_GELU, dropout=dr[1], aux_tiled=T != F32)
-        out = ops.linear_fwd(act, w2, blk.mlp.fc2.bias, F32, ops.EPI_RESIDUAL, residual=x1, dropout=dr[2],
-                             droppath=dp[1])
+        out = ops.linear_fwd(act, w2, b2, F32, ops.EPI_RESIDUAL, residual=x1, dropout=dr[2], droppath=dp[1])
         ctx.save_for_backward(x2, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, u, act, wq, wo, w1, w2)
         return out.view(B, N, D)
 
     @staticmethod
-    def _forward_x3(ctx, x2, blk, B, N, D, H, drop, wlp):
+    def _forward_x3(ctx, x2, blk, B, N, D, H, drop, wlp, bo, b2):
         """The precision knob's forward (ViTConfig dtype 'bf16x3'; tools/precision_emulate.py):
         the qkv, out-projection, fc1 and fc2 GEMMs take split-bf16 operands (weights and the
         LayerNorm / attention / GELU outputs as hi + lo, one GEMM over K' = 3K).  The LayerNorm
@@ -494,12 +565,18 @@ class _BlockFn(torch.autograd.Function):
         ln_out = ops.BF16F8 if f8 else ops.BF16X3
 
         weights = ((a_.qkv.weight,) if sq or wq8 else ()) + (a_.proj.weight, mlp.fc1.weight, mlp.fc2.weight)
+        # the fp32 tensor each weight is split from: the master or, with LayerScale, the folded W_eff
+        # (wlp then carries it: the backward's bf16 operand is its cast)
+        src = {id(p): p.detach() for p in weights}
+        if blk.ls1 is not None:
+            src[id(a_.proj.weight)], src[id(mlp.fc2.weight)] = wlp[1], wlp[3]
+            wlp = (wlp[0], ops.cast_bf16(wlp[1]), wlp[2], ops.cast_bf16(wlp[3]))
         if f8:   # the block's split weights in one launch
             pats = [3 if wq8 and i == 0 else 1 for i in range(len(weights))]
-            split_w = dict(zip(map(id, weights), ops.split_bf16f8_weights(weights, pats)))
+            split_w = dict(zip(map(id, weights), ops.split_bf16f8_weights([src[id(p)] for p in weights], pats)))
 
         def w3(p):
-            return split_w[id(p)] if f8 else split(p.detach(), 1)[0]
+            return split_w[id(p)] if f8 else split(src[id(p)], 1)[0]
         h1_3, m1, r1 = ops.layernorm_fwd(x2, n1.weight, n1.bias, blk.eps,
                                          ln_out if sq else ops.BF16F8W if wq8 else torch.bfloat16)
         # the qkv GEMM's operands: split, weight-side split, or plain bf16 (h1 and the weight's bf16 shadow)
@@ -516,14 +593,14 @@ class _BlockFn(torch.autograd.Function):
             o3, _ = split(of, 0)
             del of
             o, lse = ops.attention_fwd(qkv, B, N, H, a_.scale)
-        x1 = ops.linear_fwd(o3, w3(a_.proj.weight), a_.proj.bias, F32, ops.EPI_RESIDUAL, residual=x2, f8=f8)
+        x1 = ops.linear_fwd(o3, w3(a_.proj.weight), bo, F32, ops.EPI_RESIDUAL, residual=x2, f8=f8)
         del o3
         h2_3, m2, r2 = ops.layernorm_fwd(x1, n2.weight, n2.bias, blk.eps, ln_out)
         # GELU in the fc1 epilogue, its output split there (VITMI_EPI_SPLIT_X3 / _F8); gelu' saved
         # in the tile-native layout of the bf16 path
         act3, dg = ops.linear_fwd(h2_3, w3(mlp.fc1.weight), mlp.fc1.bias, torch.bfloat16, ops.EPI_BIAS_GELU,
                                   aux_tiled=True, split_x3=not f8, split_f8=f8, f8=f8)
-        out = ops.linear_fwd(act3, w3(mlp.fc2.weight), mlp.fc2.bias, F32, ops.EPI_RESIDUAL, residual=x1, f8=f8)
+        out = ops.linear_fwd(act3, w3(mlp.fc2.weight), b2, F32, ops.EPI_RESIDUAL, residual=x1, f8=f8)
         # the bf16 backward's operands: hi parts of the split activations (row-strided views)
         h1, h2, act = (h1_3[:, :D] if sq or wq8 else h1_3), h2_3[:, :D], act3[:, :mlp.fc1.weight.shape[0]]
         ctx.aux_tiled = True
@@ -559,13 +636,22 @@ class _BlockFn(torch.autograd.Function):
         # point; the MLP pair where du has just been written)
         wg = []
         wr = _WgradRunner()
+        # the gradient destinations of the two linears LayerScale scales (w2 / wo are then W_eff, and
+        # the wgrads and bias column sums below form dW_eff / db_eff): the sink's or, for a frozen
+        # parameter whose dW_eff / db_eff a trainable gamma still needs, a zeroed temporary
+        def dst(p, scale):
+            d = gs(p)
+            return torch.zeros_like(p) if d is None and scale is not None and gs.wants(scale.gamma) else d
+        # (fc2_bias_done: the consumer's backward has taken that destination and formed the gradient)
+        dw2, db2 = dst(mlp.fc2.weight, blk.ls2), None if ctx.bias_done else dst(mlp.fc2.bias, blk.ls2)
+        dwo, dbo = dst(a_.proj.weight, blk.ls1), dst(a_.proj.bias, blk.ls1)
         # MLP branch
         # fc1's bias gradient = column sums of du, fused into the DGELU epilogue
         du = ops.linear_dgrad(g2_lp, w2, T, ops.EPI_DGELU, aux=u, bias_grad=gs(mlp.fc1.bias), aux_tiled=ctx.aux_tiled)
-        if gs.wants(mlp.fc2.weight):
-            wg.append((g2_lp, act, gs(mlp.fc2.weight)))
-        if not ctx.bias_done and gs.wants(mlp.fc2.bias):
-            ops.bias_grad(g2_lp, gs(mlp.fc2.bias))
+        if dw2 is not None:
+            wg.append((g2_lp, act, dw2))
+        if db2 is not None:
+            ops.bias_grad(g2_lp, db2)
         if gs.wants(mlp.fc1.weight):
             wg.append((du, h2, gs(mlp.fc1.weight)))
         if ops.WGRAD_GROUP in (0, 2, 3):
@@ -575,19 +661,19 @@ class _BlockFn(torch.autograd.Function):
         # LN2 backward + residual; its column sums of dx1 are the out-proj bias grad
         if not masked:
             dx1, dx1_lp = ops.layernorm_bwd(dh2, x1, m2, r2, n2.weight, gs(n2.weight), gs(n2.bias),
-                                            dres=g2, lp_dtype=lpT, dxsum=gs(a_.proj.bias))
+                                            dres=g2, lp_dtype=lpT, dxsum=dbo)
             if dx1_lp is None:
                 dx1_lp = dx1
         else:
             dx1, _ = ops.layernorm_bwd(dh2, x1, m2, r2, n2.weight, gs(n2.weight), gs(n2.bias),
                                        dres=g2, lp_dtype=None)
             dx1_lp = _branch_grad(dx1, seed, site0, rate, psite0, prate, N, T)
-            if gs.wants(a_.proj.bias):
-                ops.bias_grad(dx1_lp, gs(a_.proj.bias))
+            if dbo is not None:
+                ops.bias_grad(dx1_lp, dbo)
         # attention branch
         do = ops.linear_dgrad(dx1_lp, wo, T)
-        if gs.wants(a_.proj.weight):
-            wg.append((dx1_lp, o, gs(a_.proj.weight)))
+        if dwo is not None:
+            wg.append((dx1_lp, o, dwo))
         if ops.WGRAD_GROUP == 0:
             wr.run(_each_wgrad, wg)
             wg = []
@@ -606,6 +692,14 @@ class _BlockFn(torch.autograd.Function):
         dx, dx_lp = ops.layernorm_bwd(dh1, x2, m1, r1, n1.weight, gs(n1.weight), gs(n1.bias),
                                       dres=dx1, lp_dtype=lpT if want_lp else None, dxsum=gs(prev))
         wr.join()
+        if blk.ls1 is not None:
+            # dW_eff is complete after the join, db_eff only after the folds queued so far: launch them
+            # now, then turn (dW_eff, db_eff) into (dgamma, dW, db) before any gradient is returned
+            ops.flush_folds()
+            for lin, scale, dw, db in ((mlp.fc2, blk.ls2, dw2, db2), (a_.proj, blk.ls1, dwo, dbo)):
+                if dw is not None or db is not None:
+                    ops.layerscale_bwd(lin.weight.detach(), lin.bias.detach(), scale.gamma.detach(), dw, db,
+                                       gs(scale.gamma), scale_grads=gs.wants(lin.weight) or gs.wants(lin.bias))
         out = _handover(dx.view(B, N, D), dx_lp)
         return (out, None, gs.grads([prev])[0], None, None, None) + gs.grads(ps)
 
@@ -983,7 +1077,7 @@ class VisionTransformer(nn.Module):
         self.pos_embed = nn.Parameter(torch.zeros(1, cfg.seq_len, D)) if cfg.pos_embed else None
         self.blocks = nn.ModuleList([
             Block(D, cfg.num_heads, cfg.mlp_ratio, cfg.qkv_bias, cfg.ln_eps, cfg.attn_scale, cfg.tie_norms,
-                  cfg.dtype) for _ in range(cfg.depth)])
+                  cfg.dtype, cfg.init_values) for _ in range(cfg.depth)])
         if cfg.split_qkv is not None:
             for blk in self.blocks:
                 blk.split_qkv = cfg.split_qkv
@@ -1004,7 +1098,9 @@ class VisionTransformer(nn.Module):
         g = torch.Generator().manual_seed(seed) if seed is not None else None
         with torch.no_grad():
             for name, p in self.named_parameters():
-                if "norm" in name:
+                if name.endswith((".ls1.gamma", ".ls2.gamma")):   # LayerScale: its constant, not a draw
+                    p.fill_(self.cfg.init_values)
+                elif "norm" in name:
                     p.fill_(1.0 if name.endswith("weight") else 0.0)
                 elif name.endswith("bias"):
                     p.zero_()
@@ -1069,7 +1165,10 @@ class VisionTransformer(nn.Module):
         # a block (the blocks see a plain model with N = K + 1): the fusion stays on.
         if not masks:
             seed = None
-        fused = self._fc2_bias_fused = seed is None
+        # LayerScale: a block's fc2 bias gradient is gamma2 o colsum, finished by that block's own
+        # backward (vitmi_layerscale_bwd), so no consumer forms it either; the bf16 gradient handover
+        # stays (the branch gradient itself is not rescaled)
+        fused = self._fc2_bias_fused = seed is None and self.cfg.init_values is None
         L = len(self.blocks)
         for i, blk in enumerate(self.blocks):
             prev_bias = self.blocks[i - 1].mlp.fc2.bias if i > 0 and fused else None
@@ -1089,6 +1188,7 @@ def build_model(cfg: ViTConfig, device="cuda") -> VisionTransformer:
     return VisionTransformer(cfg).to(device)
 
 
-__all__ = ["LayerNorm", "Linear", "Attention", "Mlp", "Block", "DropPath", "ConvEmbed", "VisionTransformer",
+__all__ = ["LayerNorm", "Linear", "Attention", "Mlp", "Block", "DropPath", "LayerScale", "ConvEmbed",
+           "VisionTransformer",
            "cross_entropy", "mse_loss", "build_model", "ParamArena"]
 

@@ -103,6 +103,17 @@ class deferred_folds:
         return False
 
 
+def flush_folds() -> None:
+    """Inside ``deferred_folds``: launch the folds queued so far and go on queueing; the gradients they
+    complete are final in the current stream's order after the call (a kernel that READS a folded
+    gradient inside the same backward, vitmi_layerscale_bwd, comes after it).  The workspaces stay
+    held until the block exits.  Outside ``deferred_folds`` folds are never queued: a no-op."""
+    if getattr(_TLS, "hold", None) is None:
+        return
+    check(lib().vitmi_fold_end(_s()), "fold_end")
+    check(lib().vitmi_fold_begin(), "fold_begin")
+
+
 def _rows(t: Tensor) -> Tuple[int, int]:
     """(rows, row stride) of a tensor viewed as [rows, last-dim] with unit inner stride."""
     if t.stride(-1) != 1 and t.shape[-1] != 1:
@@ -227,6 +238,63 @@ def droppath_apply(x: Tensor, seed: int, site: int, rate: float, rows_per_sample
     check(lib().vitmi_droppath_apply(M, N, _p(x), ldx, _p(y), dt(out_dtype), N, rows_per_sample, seed & 0xFFFFFFFF,
                                      site, pthresh, pscale, dsite, dthresh, dscale, _s()), "droppath_apply")
     return y
+
+
+# ---------------------------------------------------------------- LayerScale
+def layerscale_fold(w: Tensor, gamma: Tensor, bias: Optional[Tensor], out_dtype: torch.dtype):
+    """(W_eff, b_eff) of a LayerScale-d linear: W_eff[n, k] = gamma[n] * w[n, k] rounded once to
+    ``out_dtype`` (fp32 or bf16), b_eff = gamma * bias in fp32 (None without a bias).  w, gamma, bias:
+    the fp32 masters (vitmi_layerscale_fold)."""
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.dim() == 2
+    assert gamma.dtype == torch.float32 and gamma.is_contiguous() and gamma.numel() == w.shape[0]
+    N, K = w.shape
+    w_eff = torch.empty(N, K, dtype=out_dtype, device=w.device)
+    b_eff = None
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N
+        b_eff = torch.empty(N, dtype=torch.float32, device=w.device)
+    check(lib().vitmi_layerscale_fold(N, K, _p(w), _p(gamma), _p(bias), _p(w_eff), dt(out_dtype), _p(b_eff), _s()),
+          "layerscale_fold")
+    return w_eff, b_eff
+
+
+def layerscale_bwd(w: Tensor, bias: Optional[Tensor], gamma: Tensor, dw: Optional[Tensor], db: Optional[Tensor],
+                   dgamma: Optional[Tensor], scale_grads: bool = True) -> None:
+    """In place on the gradient destinations of a LayerScale-d linear, ``dw`` holding dW_eff and ``db``
+    db_eff: dgamma[n] += rowdot(dw[n], w[n]) + db[n] * bias[n] (``dgamma`` None: skipped), then, with
+    ``scale_grads``, dw[n] *= gamma[n] and db[n] *= gamma[n] (vitmi_layerscale_bwd).  The caller orders it
+    after everything that adds into dw / db, the deferred folds included (``flush_folds``)."""
+    N, K = w.shape
+    for t, n in ((w, N * K), (bias, N), (gamma, N), (dw, N * K), (db, N), (dgamma, N)):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n)
+    check(lib().vitmi_layerscale_bwd(N, K, _p(w), _p(bias), _p(gamma), _p(dw), _p(db), _p(dgamma),
+                                     int(bool(scale_grads)), _s()), "layerscale_bwd")
+
+
+def layerscale_apply(x: Tensor, gamma: Tensor, out_dtype: torch.dtype) -> Tensor:
+    """x (fp32, rows x C, rows may be strided) * gamma[col], in out_dtype (vitmi_layerscale_apply)."""
+    assert x.dtype == torch.float32 and gamma.dtype == torch.float32 and gamma.is_contiguous()
+    M, ldx = _rows(x)
+    N = x.shape[-1]
+    assert gamma.numel() == N
+    y = torch.empty(M, N, dtype=out_dtype, device=x.device)
+    check(lib().vitmi_layerscale_apply(M, N, _p(x), ldx, _p(gamma), _p(y), dt(out_dtype), N, _s()),
+          "layerscale_apply")
+    return y
+
+
+def layerscale_dgamma(dy: Tensor, x: Tensor, dgamma: Tensor) -> None:
+    """dgamma[col] (fp32) += sum over rows of dy[row, col] * x[row, col] (fp32, rows may be strided;
+    vitmi_layerscale_dgamma: a fixed-order two-step column reduction)."""
+    assert dy.dtype == torch.float32 and x.dtype == torch.float32
+    assert dgamma.dtype == torch.float32 and dgamma.is_contiguous()
+    M, lddy = _rows(dy)
+    M2, ldx = _rows(x)
+    N = x.shape[-1]
+    assert M2 == M and dy.shape[-1] == N and dgamma.numel() == N
+    ws = _ws(lib().vitmi_layerscale_dgamma_workspace_size(M, N), dy)
+    check(lib().vitmi_layerscale_dgamma(M, N, _p(dy), lddy, _p(x), ldx, _p(dgamma), _p(ws), ws.numel(), _s()),
+          "layerscale_dgamma")
 
 
 def linear_dgrad(dy: Tensor, w: Tensor, out_dtype: torch.dtype, epilogue: int = EPI_STORE,
