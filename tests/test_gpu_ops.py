@@ -573,7 +573,7 @@ def test_attention_bwd_fused_bias(B, N, H, T):
     db_ref = torch.full((3 * D,), 0.25, device=DEV)
     ops.bias_grad(ref, db_ref)
     db = torch.full((3 * D,), 0.25, device=DEV)
-    dqkv = ops.attention_bwd(qkv, o, do, lse, B, N, H, 0.125, bias_grad=db, fused_bias=True)
+    dqkv = ops.attention_bwd(qkv, o, do, lse, B, N, H, 0.125, bias_grad=db)
     assert torch.equal(dqkv, ref)
     # the fused sums add the same bf16-rounded values in another order
     assert rel(db, db_ref) < 1e-5

@@ -29,7 +29,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .modules import F32, LayerNorm, Linear, _check_cuda, _drop_args, _lp, _sink, cross_entropy, mse_loss  # noqa: F401
+from .modules import (F32, LayerNorm, Linear, _block_drop, _branch_grad, _branch_masks, _check_cuda, _drop_seed,  # noqa: F401
+                      _lp, _mlp_bwd, _mlp_fwd, _proj_bwd, _sink, cross_entropy, mse_loss)
 
 Tensor = torch.Tensor
 
@@ -336,16 +337,12 @@ class _CvTBlockFn(torch.autograd.Function):
             ops.gemm(inp, wl, True, True, M, D, D, qkv[:, c_i * D:(c_i + 1) * D], ops.EPI_STORE, bias=bl)
             saved_proj += [inp, z, mean, rstd, wl]
         o, lse = ops.attention_fwd(qkv, B, N, Hh, scale)
-        dr = [None, None, None]
-        if drop is not None:   # (seed, rate, site0): sites site0 (proj), +1 (GELU), +2 (fc2)
-            dr = [(drop[0], drop[2] + j, drop[1]) for j in range(3)]
+        dr, _ = _branch_masks(drop, N)   # dropout after the out-projection, the GELU and fc2; no drop path
         wo, bo = weight_of("o")
         x1 = ops.linear_fwd(o, wo, bo, F32, ops.EPI_RESIDUAL, residual=x2, dropout=dr[0])
         h2, m2, r2 = ops.layernorm_fwd(x1, n2.weight, n2.bias, cfg.ln_eps, T)
         w1, w2 = _lp(blk, blk.mlp.fc1.weight, T), _lp(blk, blk.mlp.fc2.weight, T)
-        act, u = ops.linear_fwd(h2, w1, blk.mlp.fc1.bias, T, ops.EPI_BIAS_GELU, dropout=dr[1],
-                                aux_tiled=T == torch.bfloat16)
-        out = ops.linear_fwd(act, w2, blk.mlp.fc2.bias, F32, ops.EPI_RESIDUAL, residual=x1, dropout=dr[2])
+        out, act, u = _mlp_fwd(h2, w1, blk.mlp.fc1.bias, w2, blk.mlp.fc2.bias, T, x1, dr[1:])
         ctx.save_for_backward(x2, h, m1, r1, qkv, o, lse, x1, h2, m2, r2, u, act, wo, w1, w2, *saved_proj)
         ctx.blk, ctx.dims, ctx.drop = blk, (B, N, D, H, W, with_cls, scale), drop
         return out.view(B, N, D)
@@ -365,25 +362,18 @@ class _CvTBlockFn(torch.autograd.Function):
         ps = list(blk.parameters())
         gs = _sink(ctx, 6, ps)
         g2 = dout.contiguous().view(M, D).float()
-        drop = ctx.drop
-        if drop is None:
+        dr, dp = _branch_masks(ctx.drop, N)
+        masked = dr[0] is not None
+        if not masked:
             g2_lp = g2 if T == F32 else ops.cast_bf16(g2)
         else:   # the fc2 branch was dropped: its dgrad/wgrad/bias see g2 * mask / (1 - p)
-            g2_lp = ops.dropout_apply(g2, drop[0], drop[2] + 2, drop[1], T)
-        # MLP
-        du = ops.linear_dgrad(g2_lp, w2, T, ops.EPI_DGELU, aux=u, bias_grad=gs(mlp.fc1.bias),
-                              aux_tiled=T == torch.bfloat16)
-        if gs.wants(mlp.fc2.weight):
-            ops.linear_wgrad(g2_lp, act, gs(mlp.fc2.weight))
-        if gs.wants(mlp.fc2.bias):
-            ops.bias_grad(g2_lp, gs(mlp.fc2.bias))
-        dh2 = ops.linear_dgrad(du, w1, T)
-        if gs.wants(mlp.fc1.weight):
-            ops.linear_wgrad(du, h2, gs(mlp.fc1.weight))
+            g2_lp = _branch_grad(g2, dr[2], dp[1], T)
+        dh2 = _mlp_bwd(g2_lp, h2, act, u, w1, w2, T, gs(mlp.fc1.weight), gs(mlp.fc1.bias), gs(mlp.fc2.weight),
+                       gs(mlp.fc2.bias), ops.linear_wgrad)
         dx1, dx1_lp = ops.layernorm_bwd(dh2, x1, m2, r2, n2.weight, gs(n2.weight), gs(n2.bias), dres=g2,
-                                        lp_dtype=lpT if drop is None else None)
-        if drop is not None:   # the out-projection branch was dropped
-            dx1_lp = ops.dropout_apply(dx1, drop[0], drop[2], drop[1], T)
+                                        lp_dtype=None if masked else lpT)
+        if masked:   # the out-projection branch was dropped
+            dx1_lp = _branch_grad(dx1, dr[0], dp[0], T)
         elif dx1_lp is None:
             dx1_lp = dx1
         def grads_of(c):
@@ -403,12 +393,8 @@ class _CvTBlockFn(torch.autograd.Function):
             if inner is not None and G is not None:
                 _chain(outer, inner, G, gb, gs)
         # attention + out-projection
-        do = ops.linear_dgrad(dx1_lp, wo, T)
-        ww, wb, dWo, dbo = grads_of("o")
-        if ww:
-            ops.linear_wgrad(dx1_lp, o, dWo)
-        if wb:
-            ops.bias_grad(dx1_lp, dbo)
+        _, _, dWo, dbo = grads_of("o")   # (a destination is None exactly where its gradient is not wanted)
+        do = _proj_bwd(dx1_lp, o, wo, dWo, dbo, ops.linear_wgrad)
         chain_of("o", dWo, dbo)
         dqkv = ops.attention_bwd(qkv, o, do, lse, B, N, a_.num_heads, scale)
         # q/k/v GEMMs, the cls rows, dw_bn: all into the LN1-output gradient dh
@@ -553,7 +539,8 @@ class CvT(nn.Module):
         t = None
         cap = getattr(self, "_capture_stage", None)
         stages = self.stages()
-        drop = _drop_args(self, self.cfg.drop_rate, 0)
+        rate = self.cfg.drop_rate
+        seed = _drop_seed(self, rate > 0.0)
         bi = 0   # global block index: dropout sites 3*bi .. 3*bi+2
         for si, stg in enumerate(stages):
             st = stg.spec
@@ -562,8 +549,7 @@ class CvT(nn.Module):
             if stg.cls_token is not None:
                 t = torch.cat([stg.cls_token.expand(B, 1, D), t], dim=1)
             for blk in stg.blocks:
-                d = None if drop is None else (drop[0], drop[1], 3 * bi)
-                t = blk(t, H, H, stg.cls_token is not None, d)
+                t = blk(t, H, H, stg.cls_token is not None, _block_drop(seed, rate, bi, 0.0))
                 bi += 1
             if cap is not None and si == cap % len(stages):     # Grad-CAM's activation (vitmi.gradcam)
                 if t.requires_grad:

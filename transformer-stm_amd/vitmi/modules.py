@@ -68,16 +68,78 @@ def _drop_seed(mod: nn.Module, active: bool) -> Optional[int]:
     return int(seed)
 
 
-def _drop_args(mod: nn.Module, rate: float, site0: int):
-    """(seed, rate, site0) for a training-mode forward with dropout, else None (_drop_seed)."""
-    seed = _drop_seed(mod, rate > 0.0)
-    return None if seed is None else (seed, float(rate), site0)
-
-
 def _block_drop(seed: Optional[int], rate: float, i: int, path_rate: float):
-    """_BlockFn's ``drop`` of block i: (seed, dropout rate, first dropout site, drop-path rate,
+    """A fused block's ``drop`` for block i: (seed, dropout rate, first dropout site, drop-path rate,
     first drop-path site), or None when the forward drops nothing anywhere."""
     return None if seed is None else (seed, float(rate), 3 * i, float(path_rate), _PATH_SITE0 + 2 * i)
+
+
+def _branch_masks(drop, N: int):
+    """The masks of one block from its ``drop`` (_block_drop, or None), the only place sites are
+    computed: the three ``dropout=`` triples of ops.linear_fwd (out-projection, GELU output, fc2) and
+    the two ``droppath=`` quadruples (attention branch, MLP branch; a sample is its N rows), each None
+    where its rate is 0."""
+    dr, dp = [None, None, None], [None, None]
+    if drop is not None:
+        seed, rate, site0, prate, psite0 = drop
+        if rate > 0:
+            dr = [(seed, site0 + j, rate) for j in range(3)]
+        if prate > 0:
+            dp = [(seed, psite0 + j, prate, N) for j in range(2)]
+    return dr, dp
+
+
+def _branch_grad(g: Tensor, dr, dp, T: torch.dtype) -> Tensor:
+    """``g`` (fp32 [M, D]) as the gradient entering a branch that the forward masked with ``dr`` and /
+    or ``dp`` (_branch_masks; not both None): times the element-dropout mask and / or the drop-path
+    factor of each sample, in the compute dtype; one launch either way."""
+    if dp is not None:
+        seed, psite, prate, S = dp
+        return ops.droppath_apply(g, seed, psite, prate, S, T, dropout=None if dr is None else dr[1:])
+    seed, dsite, drate = dr
+    return ops.dropout_apply(g, seed, dsite, drate, T)
+
+
+# The two branches every fused block is made of, written once: the autograd Functions below (and
+# vitmi/cvt.py's block) sequence these and keep their own saved tensors and gradient destinations.
+def _mlp_fwd(x: Tensor, w1: Tensor, b1, w2: Tensor, b2, T: torch.dtype, residual: Optional[Tensor] = None,
+             dr=(None, None), dp=None):
+    """fc1 + bias + GELU -> fc2 + bias (+ ``residual``: the RESIDUAL epilogue, else STORE) on operands of
+    the compute dtype T; ``dr`` / ``dp``: the GELU-output and fc2 dropout and the MLP branch's drop path
+    (_branch_masks).  Returns (out fp32, GELU output, gelu'); gelu' stays in the tile-native layout
+    between fc1's epilogue and fc2's dgrad (bf16)."""
+    act, u = ops.linear_fwd(x, w1, b1, T, ops.EPI_BIAS_GELU, dropout=dr[0], aux_tiled=T != F32)
+    out = ops.linear_fwd(act, w2, b2, F32, ops.EPI_STORE if residual is None else ops.EPI_RESIDUAL,
+                         residual=residual, dropout=dr[1], droppath=dp)
+    return out, act, u
+
+
+def _mlp_bwd(g: Tensor, x: Tensor, act: Tensor, u: Tensor, w1: Tensor, w2: Tensor, dx_dtype: torch.dtype,
+             dw1, db1, dw2, db2, wgrad) -> Tensor:
+    """The MLP branch's backward from ``g``, the gradient of the fc2 output in the compute dtype (masked
+    by the caller where the forward was): DGELU dgrad with fc1's bias gradient (column sums of du) fused
+    into its epilogue, fc2's bias column sums, ``wgrad(dy, x, dw)`` for fc2 then fc1, and the fc1 dgrad
+    in ``dx_dtype``, which is returned.  Each destination may be None."""
+    du = ops.linear_dgrad(g, w2, g.dtype, ops.EPI_DGELU, aux=u, bias_grad=db1, aux_tiled=g.dtype != F32)
+    if db2 is not None:
+        ops.bias_grad(g, db2)
+    if dw2 is not None:
+        wgrad(g, act, dw2)
+    if dw1 is not None:
+        wgrad(du, x, dw1)
+    return ops.linear_dgrad(du, w1, dx_dtype)
+
+
+def _proj_bwd(g: Tensor, o: Tensor, wo: Tensor, dw, db, wgrad) -> Tensor:
+    """The out-projection's backward from ``g`` (compute dtype): its dgrad, which is returned (the
+    attention output's gradient), ``wgrad(dy, x, dw)`` and the bias column sums; ``dw`` / ``db`` may be
+    None."""
+    do = ops.linear_dgrad(g, wo, g.dtype)
+    if dw is not None:
+        wgrad(g, o, dw)
+    if db is not None:
+        ops.bias_grad(g, db)
+    return do
 
 
 def _sink(ctx, first: int, params, arena=None, extra=()) -> GradSink:
@@ -263,11 +325,7 @@ class _AttentionFn(torch.autograd.Function):
         T = xo.dtype
         g = dy.contiguous().float().view(B * N, D)
         g_lp = _take_lp(g, T, dy)
-        do = ops.linear_dgrad(g_lp, wo, T)
-        if gs.wants(mod.proj.weight):
-            ops.linear_wgrad(g_lp, o, gs(mod.proj.weight))
-        if gs.wants(mod.proj.bias):
-            ops.bias_grad(g_lp, gs(mod.proj.bias))
+        do = _proj_bwd(g_lp, o, wo, gs(mod.proj.weight), gs(mod.proj.bias), ops.linear_wgrad)
         dqkv = ops.attention_bwd(qkv, o, do, lse, B, N, mod.num_heads, mod.scale, bias_grad=gs(mod.qkv.bias))
         dx = ops.linear_dgrad(dqkv, wq, F32)
         if gs.wants(mod.qkv.weight):
@@ -297,8 +355,7 @@ class _MlpFn(torch.autograd.Function):
         x2 = x.contiguous().float().view(-1, shp[-1])
         xo = x2 if T == F32 else ops.cast_bf16(x2)
         w1, w2 = _lp(mod, mod.fc1.weight, T), _lp(mod, mod.fc2.weight, T)
-        a, u = ops.linear_fwd(xo, w1, mod.fc1.bias, T, ops.EPI_BIAS_GELU, aux_tiled=T != F32)
-        y = ops.linear_fwd(a, w2, mod.fc2.bias, F32)
+        y, a, u = _mlp_fwd(xo, w1, mod.fc1.bias, w2, mod.fc2.bias, T)
         ctx.save_for_backward(xo, a, u, w1, w2)
         ctx.mod, ctx.shape = mod, shp
         return y.view(shp)
@@ -313,14 +370,8 @@ class _MlpFn(torch.autograd.Function):
         T = xo.dtype
         g = dy.contiguous().float().view(-1, dy.shape[-1])
         g_lp = _take_lp(g, T, dy)
-        du = ops.linear_dgrad(g_lp, w2, T, ops.EPI_DGELU, aux=u, bias_grad=gs(mod.fc1.bias), aux_tiled=T != F32)
-        if gs.wants(mod.fc2.weight):
-            ops.linear_wgrad(g_lp, a, gs(mod.fc2.weight))
-        if gs.wants(mod.fc2.bias):
-            ops.bias_grad(g_lp, gs(mod.fc2.bias))
-        dx = ops.linear_dgrad(du, w1, F32)
-        if gs.wants(mod.fc1.weight):
-            ops.linear_wgrad(du, xo, gs(mod.fc1.weight))
+        dx = _mlp_bwd(g_lp, xo, a, u, w1, w2, F32, gs(mod.fc1.weight), gs(mod.fc1.bias), gs(mod.fc2.weight),
+                      gs(mod.fc2.bias), ops.linear_wgrad)
         return (dx.view(ctx.shape), None) + gs.grads(ps)
 
 
@@ -469,7 +520,9 @@ class Block(nn.Module):
 
 
 class _BlockFn(torch.autograd.Function):
-    """Fused block.  ``handover``: the input was produced by a vitmi Function whose backward
+    """Fused block; its MLP and out-projection branches are the shared _mlp_fwd / _mlp_bwd / _proj_bwd
+    (also _MlpFn's, _AttentionFn's and the CvT block's), its masks _branch_masks'.
+    ``handover``: the input was produced by a vitmi Function whose backward
     takes the bf16 copy of the input gradient (the LN1 backward writes it beside the fp32
     gradient).  ``prev_fc2_bias``: the fc2 bias of the block feeding this one; its gradient is
     colsum(d input), produced for free by this block's LN1 backward and returned for that input.
@@ -513,25 +566,16 @@ class _BlockFn(torch.autograd.Function):
         ctx.blk, ctx.shape = blk, (B, N, D)
         ctx.prev_bias, ctx.bias_done, ctx.drop = prev_fc2_bias, fc2_bias_done, drop
         ctx.handover = handover
-        ctx.aux_tiled = T != F32
         if knob:
             out = _BlockFn._forward_x3(ctx, x2, blk, B, N, D, H, drop, (wq, wo, w1, w2), bo, b2)
             return out.view(B, N, D)
         h1, m1, r1 = ops.layernorm_fwd(x2, n1.weight, n1.bias, blk.eps, T)
         qkv = ops.linear_fwd(h1, wq, a_.qkv.bias, T)
         o, lse = ops.attention_fwd(qkv, B, N, H, a_.scale)
-        dr, dp = [None, None, None], [None, None]
-        if drop is not None:
-            seed, rate, site0, prate, psite0 = drop
-            if rate > 0:
-                dr = [(seed, site0 + j, rate) for j in range(3)]
-            if prate > 0:   # a sample is its N rows
-                dp = [(seed, psite0 + j, prate, N) for j in range(2)]
+        dr, dp = _branch_masks(drop, N)
         x1 = ops.linear_fwd(o, wo, bo, F32, ops.EPI_RESIDUAL, residual=x2, dropout=dr[0], droppath=dp[0])
         h2, m2, r2 = ops.layernorm_fwd(x1, n2.weight, n2.bias, blk.eps, T)
-        # gelu' stays in the tile-native layout between fc1's epilogue and fc2's dgrad (bf16)
-        act, u = ops.linear_fwd(h2, w1, blk.mlp.fc1.bias, T, ops.EPI_BIAS_GELU, dropout=dr[1], aux_tiled=T != F32)
-        out = ops.linear_fwd(act, w2, b2, F32, ops.EPI_RESIDUAL, residual=x1, dropout=dr[2], droppath=dp[1])
+        out, act, u = _mlp_fwd(h2, w1, blk.mlp.fc1.bias, w2, b2, T, x1, dr[1:], dp[1])
         ctx.save_for_backward(x2, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, u, act, wq, wo, w1, w2)
         return out.view(B, N, D)
 
@@ -603,7 +647,6 @@ class _BlockFn(torch.autograd.Function):
         out = ops.linear_fwd(act3, w3(mlp.fc2.weight), b2, F32, ops.EPI_RESIDUAL, residual=x1, f8=f8)
         # the bf16 backward's operands: hi parts of the split activations (row-strided views)
         h1, h2, act = (h1_3[:, :D] if sq or wq8 else h1_3), h2_3[:, :D], act3[:, :mlp.fc1.weight.shape[0]]
-        ctx.aux_tiled = True
         ctx.save_for_backward(x2, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, dg, act, *wlp)
         return out
 
@@ -621,21 +664,15 @@ class _BlockFn(torch.autograd.Function):
         prev = ctx.prev_bias
         gs = _sink(ctx, 6, ps, getattr(blk, "_arena", None), extra=[(2, prev)] if prev is not None else [])
         g2 = dout.contiguous().float().view(M, D)
-        drop = ctx.drop
+        dr, dp = _branch_masks(ctx.drop, N)
         # this block's own branches were masked (element dropout and / or a sample factor)
-        masked = drop is not None and (drop[1] > 0 or drop[3] > 0)
+        masked = dr[0] is not None or dp[0] is not None
         if not masked:
             g2_lp = _take_lp(g2, T, dout)
         else:
             # the fc2 branch was dropped: its dgrad/wgrad/bias see g2 * mask / (1 - p) [* sample factor]
             dout.__dict__.pop(_LP_ATTR, None)
-            seed, rate, site0, prate, psite0 = drop
-            g2_lp = _branch_grad(g2, seed, site0 + 2, rate, psite0 + 1, prate, N, T)
-        # the block's weight gradients, grouped per ops.WGRAD_GROUP (default: the out-projection's
-        # and qkv's in one split-K launch over both outputs' tiles and one reduction, at qkv's
-        # point; the MLP pair where du has just been written)
-        wg = []
-        wr = _WgradRunner()
+            g2_lp = _branch_grad(g2, dr[2], dp[1], T)
         # the gradient destinations of the two linears LayerScale scales (w2 / wo are then W_eff, and
         # the wgrads and bias column sums below form dW_eff / db_eff): the sink's or, for a frozen
         # parameter whose dW_eff / db_eff a trainable gamma still needs, a zeroed temporary
@@ -645,19 +682,17 @@ class _BlockFn(torch.autograd.Function):
         # (fc2_bias_done: the consumer's backward has taken that destination and formed the gradient)
         dw2, db2 = dst(mlp.fc2.weight, blk.ls2), None if ctx.bias_done else dst(mlp.fc2.bias, blk.ls2)
         dwo, dbo = dst(a_.proj.weight, blk.ls1), dst(a_.proj.bias, blk.ls1)
-        # MLP branch
-        # fc1's bias gradient = column sums of du, fused into the DGELU epilogue
-        du = ops.linear_dgrad(g2_lp, w2, T, ops.EPI_DGELU, aux=u, bias_grad=gs(mlp.fc1.bias), aux_tiled=ctx.aux_tiled)
-        if dw2 is not None:
-            wg.append((g2_lp, act, dw2))
-        if db2 is not None:
-            ops.bias_grad(g2_lp, db2)
-        if gs.wants(mlp.fc1.weight):
-            wg.append((du, h2, gs(mlp.fc1.weight)))
-        if ops.WGRAD_GROUP in (0, 2, 3):
-            wr.run(ops.linear_wgrad_group if ops.WGRAD_GROUP == 2 else _each_wgrad, wg)
-            wg = []
-        dh2 = ops.linear_dgrad(du, w1, T)
+        dw1 = gs(mlp.fc1.weight)
+        # the weight gradients (on the side stream): the MLP pair one launch each where du has just been
+        # written, its operands still in the caches; the out-projection's and qkv's in one grouped launch
+        # (one split-K pass over both outputs' tiles, one reduction) after the qkv dgrad ("Grouped weight gradients")
+        wr = _WgradRunner()
+        mlp_wg, attn_wg = [], []
+        def mlp_wgrad(*item):   # the pair goes to the runner together, when its last one is in
+            mlp_wg.append(item)
+            if len(mlp_wg) == (dw2 is not None) + (dw1 is not None):
+                wr.run(_each_wgrad, mlp_wg)
+        dh2 = _mlp_bwd(g2_lp, h2, act, u, w1, w2, T, dw1, gs(mlp.fc1.bias), dw2, db2, mlp_wgrad)
         # LN2 backward + residual; its column sums of dx1 are the out-proj bias grad
         if not masked:
             dx1, dx1_lp = ops.layernorm_bwd(dh2, x1, m2, r2, n2.weight, gs(n2.weight), gs(n2.bias),
@@ -667,28 +702,20 @@ class _BlockFn(torch.autograd.Function):
         else:
             dx1, _ = ops.layernorm_bwd(dh2, x1, m2, r2, n2.weight, gs(n2.weight), gs(n2.bias),
                                        dres=g2, lp_dtype=None)
-            dx1_lp = _branch_grad(dx1, seed, site0, rate, psite0, prate, N, T)
+            dx1_lp = _branch_grad(dx1, dr[0], dp[0], T)
             if dbo is not None:
                 ops.bias_grad(dx1_lp, dbo)
-        # attention branch
-        do = ops.linear_dgrad(dx1_lp, wo, T)
-        if dwo is not None:
-            wg.append((dx1_lp, o, dwo))
-        if ops.WGRAD_GROUP == 0:
-            wr.run(_each_wgrad, wg)
-            wg = []
+        # (the out-projection's bias gradient is formed above either way)
+        do = _proj_bwd(dx1_lp, o, wo, dwo, None, lambda *item: attn_wg.append(item))
         # the qkv bias gradient (column sums of dqkv) comes out of the attention backward kernels
         dqkv = ops.attention_bwd(qkv, o, do, lse, B, N, a_.num_heads, a_.scale, bias_grad=gs(a_.qkv.bias))
-        if gs.wants(a_.qkv.weight):
-            wg.append((dqkv, h1, gs(a_.qkv.weight)))
-        if ops.WGRAD_GROUP == 0:
-            wr.run(_each_wgrad, wg)
-            wg = []
         dh1 = ops.linear_dgrad(dqkv, wq, T)
-        wr.run(ops.linear_wgrad_group, wg)
+        if gs.wants(a_.qkv.weight):
+            attn_wg.append((dqkv, h1, gs(a_.qkv.weight)))
+        wr.run(ops.linear_wgrad_group, attn_wg)
         # the bf16 copy of dx is for a consumer that takes it (the block below); the patch
         # embedding's backward reads dx in fp32
-        want_lp = drop is None and ctx.handover
+        want_lp = ctx.drop is None and ctx.handover
         dx, dx_lp = ops.layernorm_bwd(dh1, x2, m1, r1, n1.weight, gs(n1.weight), gs(n1.bias),
                                       dres=dx1, lp_dtype=lpT if want_lp else None, dxsum=gs(prev))
         wr.join()
@@ -702,16 +729,6 @@ class _BlockFn(torch.autograd.Function):
                                        gs(scale.gamma), scale_grads=gs.wants(lin.weight) or gs.wants(lin.bias))
         out = _handover(dx.view(B, N, D), dx_lp)
         return (out, None, gs.grads([prev])[0], None, None, None) + gs.grads(ps)
-
-
-def _branch_grad(g: Tensor, seed: int, dsite: int, drate: float, psite: int, prate: float, S: int,
-                 T: torch.dtype) -> Tensor:
-    """``g`` (fp32 [M, D]) as the gradient entering a branch that the forward masked: times the
-    element-dropout mask of (dsite, drate) and / or the drop-path factor of (psite, prate) of each
-    S-row sample, in the compute dtype; one launch either way."""
-    if prate > 0:
-        return ops.droppath_apply(g, seed, psite, prate, S, T, dropout=(dsite, drate))
-    return ops.dropout_apply(g, seed, dsite, drate, T)
 
 
 # the block backward's weight gradients on a side stream (VITMI_WGRAD_STREAM=0: the current one).

@@ -8,7 +8,6 @@ fallback — a missing library or a bad shape raises.
 from __future__ import annotations
 
 import ctypes
-import os
 import threading
 from typing import Optional, Tuple
 
@@ -324,12 +323,6 @@ def linear_dgrad(dy: Tensor, w: Tensor, out_dtype: torch.dtype, epilogue: int = 
     return dx
 
 
-
-
-def bias_grad_(dy: Tensor, db: Tensor) -> None:
-    bias_grad(dy, db)
-
-
 def linear_wgrad(dy: Tensor, x: Tensor, dw: Tensor) -> None:
     """dw[N,K] (fp32) += dy[M,N]^T x[M,K].  x may be row-strided (the hi part of a split
     operand); then the generic GEMM entry point takes its row stride."""
@@ -346,18 +339,6 @@ def linear_wgrad(dy: Tensor, x: Tensor, dw: Tensor) -> None:
                                    _s()), "linear_wgrad")
 
 
-# How a block's backward groups its weight gradients (vitmi/modules.py _BlockFn.backward): 0 = one
-# launch per problem where each gradient's operands are ready, 1 = all four in one launch at the end,
-# 2 = the MLP pair at fc1's point and the attention pair at qkv's, 3 = only the attention pair
-# (out-projection + qkv) grouped, at qkv's point.  Measured (profiles/r06_wgg/): alone, one grouped
-# launch of all four is 52 us (ViT-B) / 79 us (ViT-L) faster than four; in the step the MLP
-# weight gradients run faster where the DGELU GEMM has just written du (their operands still in
-# the caches), so 1 loses that and 3 keeps it: C3 kernel time per step 36.16 (0) / 36.35 (1) /
-# 36.00 ms (3), the out-projection's 28 slabs of 28 K-steps become 7 of 113.
-WGRAD_GROUP = int(os.environ.get("VITMI_WGRAD_GROUP", "3"))
-_WGRAD_GROUP = WGRAD_GROUP != 0
-
-
 def linear_wgrad_group(items) -> None:
     """For each (dy[M, N_p], x[M, K_p], dw[N_p, K_p]) of ``items`` (at most 4, one row count M):
     dw (fp32) += dy^T x, all in ONE split-K launch and one reduction (vitmi_linear_wgrad_group; the
@@ -365,10 +346,6 @@ def linear_wgrad_group(items) -> None:
     operand).  Mixed dtypes, other row counts or more than 4 items run one linear_wgrad each."""
     items = [t for t in items if t is not None]
     if not items:
-        return
-    if not _WGRAD_GROUP:   # (A/B switch: VITMI_WGRAD_GROUP=0 runs one launch per problem)
-        for dy, x, dw in items:
-            linear_wgrad(dy, x, dw)
         return
     M = items[0][0].numel() // items[0][0].shape[-1]
     dt0 = items[0][0].dtype
@@ -517,21 +494,15 @@ def attention_fwd_f8(qkv: Tensor, B: int, N: int, H: int, scale: float):
 
 
 def attention_bwd(qkv: Tensor, o: Tensor, do: Tensor, lse: Tensor, B: int, N: int, H: int,
-                  scale: float, bias_grad: Optional[Tensor] = None, fused_bias: bool = True) -> Tensor:
-    """dqkv; ``bias_grad`` (fp32 [3D]) += its column sums (the q/k/v bias gradient).
-
-    ``fused_bias`` (default) forms the sums in the backward kernels from the LDS image each
-    output tile is stored through (vitmi_attention_bwd_bias: one [3D] partial row per batch, or
-    per (batch, 128-row block) for N > 256, folded in a fixed order), instead of a second pass
-    over dqkv; ``fused_bias=False`` runs the
-    separate column-sum pass (kernels without the fused sums fall back to it anyway)."""
+                  scale: float, bias_grad: Optional[Tensor] = None) -> Tensor:
+    """dqkv; ``bias_grad`` (fp32 [3D]) += its column sums (the q/k/v bias gradient), formed in the
+    backward kernels from the LDS image each output tile is stored through (vitmi_attention_bwd_bias:
+    one [3D] partial row per batch, or per (batch, 128-row block) for N > 256, folded in a fixed order)
+    instead of a second pass over dqkv; the library runs that pass itself for the kernels without the
+    fused sums."""
     D = o.shape[-1]
     assert do.is_contiguous() and do.dtype == qkv.dtype
     dqkv = torch.empty_like(qkv)
-    if bias_grad is not None and not fused_bias:
-        dqkv = attention_bwd(qkv, o, do, lse, B, N, H, scale)
-        bias_grad_(dqkv, bias_grad)
-        return dqkv
     if bias_grad is not None:
         assert bias_grad.dtype == torch.float32 and bias_grad.numel() == 3 * D and bias_grad.is_contiguous()
         ws = _ws(lib().vitmi_attention_bwd_bias_workspace_size(B, N, H), qkv)
