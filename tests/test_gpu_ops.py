@@ -475,7 +475,8 @@ def test_attention_persistent_many_pairs(B, N, H):
         assert rel(d[:, i], g[:, i]) < 2e-2, name
 
 
-@pytest.mark.parametrize("B,N,H", [(48, 197, 12), (3, 224, 2), (2, 193, 1), (5, 64, 3), (2, 250, 2)])
+@pytest.mark.parametrize("B,N,H", [(48, 197, 12), (3, 224, 2), (2, 193, 1), (5, 64, 3), (2, 250, 2), (1, 1, 2), (2, 33, 1),
+                                   (2, 256, 2)])
 def test_attention_64query_forms_bitwise_equal(B, N, H):
     """The whole-sequence forward and dQ run 4 waves of 64 queries (attn_fwd_seq64_bf16,
     attn_bwd_dq_seq64_bf16; policies 0 and 3); policy 2 runs the 32-query forms.  Per query block
@@ -501,7 +502,7 @@ def test_attention_64query_forms_bitwise_equal(B, N, H):
         assert torch.equal(a, b), name
 
 
-@pytest.mark.parametrize("B,N,H", [(16, 197, 12), (3, 250, 2), (2, 33, 1)])
+@pytest.mark.parametrize("B,N,H", [(16, 197, 12), (3, 250, 2), (2, 33, 1), (1, 1, 2), (2, 256, 2)])
 def test_attention_fwd_knob_outputs_64query_bitwise_equal(B, N, H):
     """The precision knobs' attention forward (vitmi_attention_fwd_x3 / _f8) in its 64-query form
     (auto policy, round 6) against the 32-query form (policy 2): o, lse and the split outputs o3 /

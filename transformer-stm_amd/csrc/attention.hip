@@ -212,13 +212,14 @@ __device__ __forceinline__ void store_tile32_f8(char* scr, const f32x16 (&acc)[2
   asm volatile("" ::: "memory");
 }
 
-// Column sums of the rows < nvalid of the tile store_tile32 just wrote (its LDS image, as the
-// stored bf16 values): each lane adds 4 rows x 8 columns, xor-shuffles fold the 8 row groups,
-// and the block's waves (all of which must call) fold through red[wave][64] in wave order into
-// colpart[0..63] -- a bias-gradient partial without a second pass over the stored matrix, in a
-// fixed summation order.
-__device__ __forceinline__ void tile32_colsum(const char* scr, int row0, int nvalid, float* colpart,
-                                              float (*red)[64], int wave, int nw, int lane) {
+// Column sums of the stored matrix without a second pass over it (a bias-gradient partial), in a
+// fixed summation order, in two parts.
+// Part 1, per 32-row block: the sums over the rows < nvalid of the tile store_tile32 just wrote
+// (its LDS image, as the stored bf16 values) into red_row[0..63]: each lane adds 4 rows x 8
+// columns, xor-shuffles fold the 8 row groups.  red_reused: red_row may still be read by an
+// earlier fold, so the block's waves (all of which must call) meet at a barrier before writing it.
+__device__ __forceinline__ void tile32_rowsums(const char* scr, int row0, int nvalid, float* red_row, int lane,
+                                               bool red_reused) {
   const int rr = lane >> 3, cc = lane & 7;
   float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -235,17 +236,26 @@ __device__ __forceinline__ void tile32_colsum(const char* scr, int row0, int nva
     cs[e] += __shfl_xor(cs[e], 16, 64);
     cs[e] += __shfl_xor(cs[e], 32, 64);
   }
-  __syncthreads();                       // red is free (an earlier call's fold is done)
+  if (red_reused) __syncthreads();
   if (lane < 8) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) red[wave][lane * 8 + e] = cs[e];
+    for (int e = 0; e < 8; ++e) red_row[lane * 8 + e] = cs[e];
   }
-  __syncthreads();
+}
+// Part 2, after a barrier: the rows red[0 .. nblk) fold in block order into colpart[0..63].
+__device__ __forceinline__ void colsum_fold(const float (*red)[64], int nblk, float* colpart) {
   if (threadIdx.x < 64) {
     float t = 0.f;
-    for (int w = 0; w < nw; ++w) t += red[w][threadIdx.x];
+    for (int w = 0; w < nblk; ++w) t += red[w][threadIdx.x];
     colpart[threadIdx.x] = t;
   }
+}
+// Both parts for kernels whose wave w holds block w (all waves must call; red is reused)
+__device__ __forceinline__ void tile32_colsum(const char* scr, int row0, int nvalid, float* colpart,
+                                              float (*red)[64], int wave, int nw, int lane) {
+  tile32_rowsums(scr, row0, nvalid, red[wave], lane, true);
+  __syncthreads();
+  colsum_fold(red, nw, colpart);
 }
 
 // =============================================================== forward (bf16)
@@ -676,22 +686,10 @@ __device__ __forceinline__ float asm_load4(__amdgpu_buffer_rsrc_t rs, uint32_t v
 }
 
 #ifdef VITMI_ATTN_STAMPS
-// DIAGNOSTIC build only: [kernel 0 fwd / 1 dQ][pair][8] = s_memrealtime at start, operands
-// landed, loop done, end; then HW_ID and XCC_ID (tools/attn_stamps.py)
+// DIAGNOSTIC build only (tools/attn_fused_stamps.py): s_memrealtime stamps of the single-pass
+// backward, table [2][pair][8] (tables 0 and 1 are unused) = pair start (its loads landed), phase 1
+// start, phase 1 done, phase 2 done, epilogue done; HW_ID, XCC_ID in [6], [7]
 __device__ unsigned long long* d_attn_stamps;
-#define ATTN_STAMP(kern, k)                                                                          \
-  do {                                                                                               \
-    if (d_attn_stamps && threadIdx.x == 0) {                                                         \
-      unsigned long long* p_ = d_attn_stamps + ((int64_t)(kern) * 65536 + blockIdx.x) * 8;           \
-      p_[k] = __builtin_amdgcn_s_memrealtime();                                                      \
-      if ((k) == 0) {                                                                                \
-        p_[4] = __builtin_amdgcn_s_getreg(4 | (31 << 11));                                           \
-        p_[5] = __builtin_amdgcn_s_getreg(20 | (15 << 11));                                          \
-      }                                                                                              \
-    }                                                                                                \
-  } while (0)
-// the single-pass backward: [2][pair][8] = pair start (its loads landed), phase 1 start, phase 1
-// done, phase 2 done, epilogue done; HW_ID, XCC_ID in [6], [7]
 #define FUSED_STAMP(pair, k)                                                                         \
   do {                                                                                               \
     if (d_attn_stamps && threadIdx.x == 0) {                                                         \
@@ -704,7 +702,6 @@ __device__ unsigned long long* d_attn_stamps;
     }                                                                                                \
   } while (0)
 #else
-#define ATTN_STAMP(kern, k) do {} while (0)
 #define FUSED_STAMP(pair, k) do {} while (0)
 #endif
 
@@ -743,7 +740,6 @@ __global__ __launch_bounds__(NPMAX * 2, 4) void attn_fwd_seq_bf16(const bf16* __
   __amdgpu_buffer_rsrc_t rq = make_rsrc(base + hd * DH, bytes - hd * DH * 2);
   __amdgpu_buffer_rsrc_t rk = make_rsrc(base + D + hd * DH, bytes - (D + hd * DH) * 2);
   __amdgpu_buffer_rsrc_t rv = make_rsrc(base + 2 * D + hd * DH, bytes - (2 * D + hd * DH) * 2);
-  ATTN_STAMP(0, 0);
   char* kt = smem;
   char* vt = smem + NP * 128;
   stage_seq(kt, rk, ldb, NP, nw, wave, lane);
@@ -754,7 +750,6 @@ __global__ __launch_bounds__(NPMAX * 2, 4) void attn_fwd_seq_bf16(const bf16* __
   for (int s = 0; s < 4; ++s) qf[s] = load_row16(rq, (uint32_t)((int64_t)q * ldb + (16 * s + 8 * h) * 2));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  ATTN_STAMP(0, 1);
 
   const float c2 = scale * LOG2E;
   float m = -INFINITY, l = 0.f;
@@ -826,12 +821,10 @@ __global__ __launch_bounds__(NPMAX * 2, 4) void attn_fwd_seq_bf16(const bf16* __
   if (q < N && h == 0) lse[(int64_t)bh * N + q] = (m + log2f(lt)) * LN2;
   // O through the (now free) K/V image: every wave must be done reading it
   __syncthreads();
-  ATTN_STAMP(0, 2);
   const int64_t ldo = (int64_t)D * 2;
   const __amdgpu_buffer_rsrc_t ro = make_rsrc(o + (int64_t)b * N * D + hd * DH, (uint32_t)((int64_t)N * ldo - hd * DH * 2));
   const float inv = 1.f / lt;
   store_tile32(smem + wave * ST_BYTES, oacc, inv, ro, ldo, wave * 32, lane_here());
-  ATTN_STAMP(0, 3);
   if constexpr (XM == 2) {
     // hi (bf16) at columns [0, D) of the 2D-wide row, the head's e4m3 block [hi8 | lo8] at byte
     // 2D + 128 hd
@@ -1046,15 +1039,11 @@ __global__ __launch_bounds__(NPMAX * 2, 4) void attn_bwd_dq_seq_bf16(
     const bf16* __restrict__ qkv, const bf16* __restrict__ o, const bf16* __restrict__ dout,
     const float* __restrict__ lse, float* __restrict__ delta, bf16* __restrict__ dqkv, int N, int H,
     float scale, float* __restrict__ colsum) {
-  // K | V images; after the loop also the [NP][65] fp32 image of the fused bias column sums
-  constexpr int SMEM = 2 * NPMAX * 128 > NPMAX * 65 * 4 ? 2 * NPMAX * 128 : NPMAX * 65 * 4;
-  __shared__ __attribute__((aligned(16))) char smem[SMEM];
+  __shared__ __attribute__((aligned(16))) char smem[2 * NPMAX * 128];   // K | V images
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nw = NWC > 0 ? NWC : blockDim.x >> 6, NP = nw * 32;
-  // pairs in DESCENDING order: the producer of this kernel's operand (the qkv GEMM for the
-  // forward, the out-proj dgrad writing dO for dQ) finished with the last rows, which are the
-  // ones still in the MALL; the dK/dV kernel after dQ then walks ascending (dQ ended at pair 0)
+  // pairs in DESCENDING order (attn_fwd_seq_bf16's note)
   const int bh = gridDim.x - 1 - blockIdx.x, b = bh / H, hd = bh % H;
   const int D = H * DH;
   const int64_t ld = 3 * (int64_t)D, ldb = ld * 2, ldo = (int64_t)D * 2;
@@ -1067,7 +1056,6 @@ __global__ __launch_bounds__(NPMAX * 2, 4) void attn_bwd_dq_seq_bf16(
   __amdgpu_buffer_rsrc_t rv = make_rsrc(base + 2 * D + hd * DH, bytes - (2 * D + hd * DH) * 2);
   __amdgpu_buffer_rsrc_t rdo = make_rsrc(dout + (int64_t)b * N * D + hd * DH, obytes - hd * DH * 2);
   __amdgpu_buffer_rsrc_t ro = make_rsrc(o + (int64_t)b * N * D + hd * DH, obytes - hd * DH * 2);
-  ATTN_STAMP(1, 0);
   char* kt = smem;
   char* vt = smem + NP * 128;
   stage_seq(kt, rk, ldb, NP, nw, wave, lane);
@@ -1099,7 +1087,6 @@ __global__ __launch_bounds__(NPMAX * 2, 4) void attn_bwd_dq_seq_bf16(
   const float L2 = qok ? lse[(int64_t)bh * N + q] * LOG2E : INFINITY;   // q >= N -> p = 0
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  ATTN_STAMP(1, 1);
 
   const float c2 = scale * LOG2E;
   f32x16 dqt[2] = {zero16(), zero16()};
@@ -1140,11 +1127,9 @@ __global__ __launch_bounds__(NPMAX * 2, 4) void attn_bwd_dq_seq_bf16(
   // dQ through the (now free) K/V image: every wave must be done reading it.  With colsum,
   // also this head's q-bias gradient partial colsum[b][hd*64 ..] (column sums of the stored dQ)
   __syncthreads();
-  ATTN_STAMP(1, 2);
   const __amdgpu_buffer_rsrc_t rdq = make_rsrc(dqkv + (int64_t)b * N * ld + hd * DH, bytes - hd * DH * 2);
   const int ln = lane_here();
   store_tile32(smem + wave * ST_BYTES, dqt, scale, rdq, ldb, wave * 32, ln);
-  ATTN_STAMP(1, 3);
   if (colsum) {
     __shared__ float red[NPMAX / 32][64];
     tile32_colsum(smem + wave * ST_BYTES, wave * 32, N, colsum + (int64_t)b * 3 * D + hd * DH, red, wave, nw, ln);
@@ -1259,32 +1244,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_seq64_bf16(
     for (int k0 = 0; k0 < NP; k0 += 32) kblock(k0);
     __syncthreads();   // dQ through the (now free) K/V image
     const int ln = lane_here();
-    const int rr = ln >> 3, cc = ln & 7;
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
       const int row0 = q0 + 32 * qb;
       store_tile32(smem + wave * ST_BYTES, dqt[qb], scale, rdq, ldb, row0, ln);
-      if (colsum) {   // this block's column sums (tile32_colsum's first half), folded below
-        float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const char* scr = smem + wave * ST_BYTES;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (row0 + 8 * j + rr < N) {
-            const bf16x8 v = *(const bf16x8*)(scr + (8 * j + rr) * ST_PITCH + cc * 16);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) cs[e] += (float)v[e];
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          cs[e] += __shfl_xor(cs[e], 8, 64);
-          cs[e] += __shfl_xor(cs[e], 16, 64);
-          cs[e] += __shfl_xor(cs[e], 32, 64);
-        }
-        if (ln < 8) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) red[2 * wave + qb][ln * 8 + e] = cs[e];
-        }
+      if (colsum) {   // this block's column sums, folded below
+        tile32_rowsums(smem + wave * ST_BYTES, row0, N, red[2 * wave + qb], ln, false);
         asm volatile("" ::: "memory");   // the next store_tile32 rewrites the image these reads used
       }
     }
@@ -1294,11 +1259,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_seq64_bf16(
   else __syncthreads();
   if (colsum) {
     __syncthreads();
-    if (threadIdx.x < 64) {
-      float t = 0.f;
-      for (int blk = 0; blk < NKB; ++blk) t += red[blk][threadIdx.x];
-      colsum[(int64_t)b * 3 * D + hd * DH + threadIdx.x] = t;
-    }
+    colsum_fold(red, NKB, colsum + (int64_t)b * 3 * D + hd * DH);
   }
 }
 
@@ -2232,6 +2193,8 @@ struct AttnPlan {
   bool q64;          // SEQ_BF16: the 64-query forward / dQ forms
   bool fused;        // SEQ_BF16: the single-pass backward
   int nkb;           // ceil(N / 32): waves of the 32-query forms, NKB of the single-pass backward
+  int seq_nkb;       // SEQ_BF16 two-kernel backward: nkb as its kernels' compile-time block count (7: N in
+                     // (192, 224], the ViT-B / ViT-S shape N = 197), or 0 (their runtime loops)
   int colsum_rows;   // bias-gradient partial rows per batch that the backward kernels form (0: none)
 };
 static AttnPlan attn_plan(int dtype, int N) {
@@ -2239,6 +2202,7 @@ static AttnPlan attn_plan(int dtype, int N) {
   AttnPlan p;
   p.path = bf ? (seq ? SEQ_BF16 : STREAM_BF16) : (seq ? SEQ_F32 : STREAM_F32);
   p.nkb = (N + 31) / 32;
+  p.seq_nkb = p.nkb == 7 ? 7 : 0;
   p.q64 = g_attn_policy != 2;
   p.fused = g_attn_policy == 0 && p.nkb <= FUSED_NKB;
   // one row per batch (whole-sequence kernels) or per (batch, 128-row block); the fp32 kernels form none
@@ -2391,21 +2355,16 @@ static int attention_bwd_impl(int dtype, int B, int N, int H, int dh, float scal
     }
   } else if (p.path == SEQ_BF16) {
     // dQ first: it also writes delta, which the dK/dV kernel consumes
-    if (p.nkb == 7) {   // N in (192, 224]: the ViT-B/ViT-S shape, N = 197
-      if (p.q64)
-        launch(attn_bwd_dq_seq64_bf16<SEQ_MAX, 7>, pairs, dim3(256), s, fl, by, q16, o16, do16, lse, delta, (bf16*)dqkv,
-               N, H, scale, colsum);
-      else
-        launch(attn_bwd_dq_seq_bf16<SEQ_MAX, 7>, pairs, waves, s, fl, by, q16, o16, do16, lse, delta, (bf16*)dqkv, N, H,
-               scale, colsum);
-      launch(attn_bwd_dkv_seq_bf16<SEQ_MAX, 7>, cus, waves, s, fl, by, q16, do16, lse, (const float*)delta,
-             (bf16*)dqkv, N, H, scale, colsum, npairs);
-    } else {
-      launch(attn_bwd_dq_seq_bf16<SEQ_MAX>, pairs, waves, s, fl, by, q16, o16, do16, lse, delta, (bf16*)dqkv, N, H,
-             scale, colsum);
-      launch(attn_bwd_dkv_seq_bf16<SEQ_MAX>, cus, waves, s, fl, by, q16, do16, lse, (const float*)delta, (bf16*)dqkv,
-             N, H, scale, colsum, npairs);
-    }
+    const auto run = [&](auto dq, dim3 dq_block, auto dkv) {
+      launch(dq, pairs, dq_block, s, fl, by, q16, o16, do16, lse, delta, (bf16*)dqkv, N, H, scale, colsum);
+      launch(dkv, cus, waves, s, fl, by, q16, do16, lse, (const float*)delta, (bf16*)dqkv, N, H, scale, colsum, npairs);
+    };
+    if (p.seq_nkb == 7 && p.q64)
+      run(attn_bwd_dq_seq64_bf16<SEQ_MAX, 7>, dim3(256), attn_bwd_dkv_seq_bf16<SEQ_MAX, 7>);
+    else if (p.seq_nkb == 7)
+      run(attn_bwd_dq_seq_bf16<SEQ_MAX, 7>, waves, attn_bwd_dkv_seq_bf16<SEQ_MAX, 7>);
+    else
+      run(attn_bwd_dq_seq_bf16<SEQ_MAX, 0>, waves, attn_bwd_dkv_seq_bf16<SEQ_MAX, 0>);
   } else if (p.path == STREAM_BF16) {
     // dQ first: it also writes delta, which the dK/dV kernel consumes
     const dim3 grid((N + 127) / 128, B * H);
