@@ -173,7 +173,11 @@ int vitmi_linear_wgrad_group(int dtype, int n, int64_t M, const int64_t* N, cons
                              vitmi_stream_t stream);
 size_t vitmi_linear_wgrad_group_workspace_size(int dtype, int n, int64_t M, const int64_t* N,
                                                const int64_t* K);
-/* db[N] (f32) += sum_m dy[m, n]  (dy [M][ldy] of `dtype`) */
+/* db[N] (f32) += sum_m dy[m, n]  (dy [M][ldy] of `dtype`).
+ * Preconditions (VITMI_ERR_INVALID otherwise, nothing launched): dtype VITMI_F32 or VITMI_BF16; ldy >= N;
+ * dy and db aligned to their element; workspace >= vitmi_bias_grad_workspace_size(M, N).  A 16-byte
+ * aligned dy with N % 8 == 0 and ldy % 8 == 0 takes the vector kernel, anything else the one-column-
+ * per-thread kernel.  M == 0 or N == 0 leaves db untouched. */
 int vitmi_bias_grad(int dtype, int64_t M, int64_t N, const void* dy, int64_t ldy, float* db,
                     void* workspace, size_t ws_bytes, vitmi_stream_t stream);
 size_t vitmi_bias_grad_workspace_size(int64_t M, int64_t N);
@@ -182,14 +186,26 @@ size_t vitmi_bias_grad_workspace_size(int64_t M, int64_t N);
  * LayerNorm over the last dim D (layers.LayerNormalization, models/CvT(Par).py:248,328;
  * old_codes/MS_CvT.py:39-45).  x is fp32 [M][ldx]; y [M][ldy] of y_dtype; mean/rstd fp32 [M].
  * y_dtype VITMI_BF16X3: y is bf16 [M][ldy >= 3D], each row [hi | hi | lo] of the fp32 result.
- * y_dtype VITMI_BF16F8: y is [M][ldy >= 2D] bf16 units, each row the VITMI_BF16F8 A-operand layout.
+ * y_dtype VITMI_BF16F8: y is [M][ldy >= 2D] bf16 units, each row the VITMI_BF16F8 A-operand layout
+ *   [hi | e4m3 part in 64-column blocks hi8 | lo8]; D % 64 == 0.
+ * y_dtype VITMI_BF16F8W: y is [M][ldy >= 1.5D] bf16 units, each row [hi | hi8] (one e4m3 byte per
+ *   column); D % 128 == 0.
+ * Preconditions (VITMI_ERR_INVALID otherwise, nothing launched): D % 4 == 0, 4 <= D <= 2048; ldx and
+ * ldy multiples of 4 (elements of x, resp. bf16 / fp32 units of y), ldx >= D and ldy >= the row width
+ * above; y_dtype one of the five named; x, gamma, beta and an fp32 y 16-byte aligned, every bf16-unit
+ * y 8-byte aligned (every access is a 4-element vector).  M == 0 returns VITMI_OK and writes nothing.
  */
 int vitmi_layernorm_fwd(int64_t M, int D, const float* x, int64_t ldx, const float* gamma,
                         const float* beta, float eps, void* y, int y_dtype, int64_t ldy,
                         float* mean, float* rstd, vitmi_stream_t stream);
 /* dx = dres + LN'(dy); optional low-precision copy dx_lp (bf16); dgamma/dbeta += (fp32);
  * optional dxsum[D] += column sums of dx (the bias gradient of the Dense layer whose output
- * gradient dx is: fused so that gradient is never re-read). NULL pointers skip outputs. */
+ * gradient dx is: fused so that gradient is never re-read). NULL pointers skip outputs.
+ * Preconditions (VITMI_ERR_INVALID otherwise, nothing launched): D as in the forward; dy_dtype
+ * VITMI_F32 or VITMI_BF16 (the split forms are forward outputs only); lddy, ldx, lddx, and ldres /
+ * lddx_lp when dres / dx_lp is given, multiples of 4 and >= D; x, gamma, dres, dx and an fp32 dy
+ * 16-byte aligned, a bf16 dy and dx_lp 8-byte aligned; workspace >=
+ * vitmi_layernorm_bwd_workspace_size(M, D).  M == 0 returns VITMI_OK and writes nothing. */
 int vitmi_layernorm_bwd(int64_t M, int D, const void* dy, int dy_dtype, int64_t lddy,
                         const float* x, int64_t ldx, const float* mean, const float* rstd,
                         const float* gamma, const float* dres, int64_t ldres, float* dx,

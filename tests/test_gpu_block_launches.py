@@ -18,12 +18,12 @@ substring of the recorded kernel name:
   splitk_reduce        splitk_reduce_kernel + splitk_reduce_small_kernel (a split-K weight gradient)
   splitk_reduce_group  the grouped weight gradient's reduction (its GEMM instance is a gemm256_kernel)
   ln_fwd / ln_bwd      ln_fwd_kernel / ln_bwd_kernel
+  ln_fwd_small / ln_bwd_small   the D = 64 / 128 kernels (ln_fwd_small_kernel / ln_bwd_small_kernel): every
+                       LayerNorm here but the knobs' split-output forward and the CvT's D = 256 ones
   attn_fwd / attn_bwd  bf16 at N = 17: one single-pass backward kernel; fp32: dQ then dK/dV
   cast, droppath_apply, layerscale_fold, layerscale_bwd, fold (fold_kernel, not layerscale_fold_kernel)
-What the statistics do not record, and OPS therefore carries: the D = 64 / 128 LayerNorm kernels
-(ln_fwd_small_kernel / ln_bwd_small_kernel: every LayerNorm here but the knobs' split-output forward and
-the CvT's D = 256 ones),
-vitmi_dropout_apply, and the column-sum kernel of bias_grad for a row length that is no multiple of 8.
+What the statistics do not record, and OPS therefore carries: vitmi_dropout_apply.  (The column-sum
+kernels of bias_grad are recorded and not tabled here: OPS carries the bias_grad calls.)
 At these shapes (M = B N = 51 rows) the library runs a grouped weight gradient one problem at a time
 (vitmi_linear_wgrad_group groups from 256 rows on) and no weight gradient splits K (fewer than 4
 K-steps), so both reduce families are 0 for the ViT cases and the grouping shows in OPS alone; the
@@ -50,6 +50,8 @@ FAMILIES = {
     "splitk_reduce_group": ("splitk_reduce_group_kernel",),
     "ln_fwd": ("ln_fwd_kernel",),
     "ln_bwd": ("ln_bwd_kernel",),
+    "ln_fwd_small": ("ln_fwd_small_kernel",),
+    "ln_bwd_small": ("ln_bwd_small_kernel",),
     "attn_fwd": ("attn_fwd",),
     "attn_bwd": ("attn_bwd",),
     "cast": ("cast_kernel",),
@@ -203,8 +205,8 @@ def _with(base, **kw):
 BLOCK_OPS = dict(linear_fwd=4, linear_dgrad=4, linear_wgrad=2, wgrad_group=(2,), bias_grad=1, gemm=0,
                  layernorm_fwd=2, layernorm_bwd=2, attention_fwd=1, attention_bwd=1, cast_bf16=5, dropout_apply=0,
                  droppath_apply=0, layerscale_fold=0, layerscale_bwd=0)
-BLOCK_K = dict(gemm=12, splitk_reduce=0, splitk_reduce_group=0, ln_fwd=0, ln_bwd=0, attn_fwd=1, attn_bwd=1, cast=5,
-               droppath_apply=0, layerscale_fold=0, layerscale_bwd=0, fold=1)
+BLOCK_K = dict(gemm=12, splitk_reduce=0, splitk_reduce_group=0, ln_fwd=0, ln_bwd=0, ln_fwd_small=2, ln_bwd_small=2,
+               attn_fwd=1, attn_bwd=1, cast=5, droppath_apply=0, layerscale_fold=0, layerscale_bwd=0, fold=1)
 # masked branches: no cast of the incoming gradient (the mask pass writes the compute dtype), one mask
 # pass per branch, and the out-projection's bias sums from a column-sum pass over the masked gradient
 MASKED_OPS = _with(BLOCK_OPS, cast_bf16=4, bias_grad=2)
@@ -215,7 +217,7 @@ LS_K = _with(BLOCK_K, cast=3, layerscale_fold=2, layerscale_bwd=2)
 # the precision knobs: split-output LayerNorm forwards (recorded), the bf16 backward on row-strided hi
 # parts (the MLP pair's linear_wgrad goes through ops.gemm)
 KNOB_OPS = _with(BLOCK_OPS, gemm=2)
-KNOB_K = _with(BLOCK_K, ln_fwd=2)
+KNOB_K = _with(BLOCK_K, ln_fwd=2, ln_fwd_small=0)
 # 2-block VisionTransformer: the arena's bf16 shadow is the one cast (no weight casts, and both blocks
 # take the handed-over bf16 gradient); the patch GEMM and its weight gradient run inside the
 # patch-embedding entry points; head LayerNorm; no bias_grad (each fc2 bias gradient comes out of its
@@ -223,11 +225,11 @@ KNOB_K = _with(BLOCK_K, ln_fwd=2)
 VIT_OPS = dict(linear_fwd=8, linear_dgrad=8, linear_wgrad=4, wgrad_group=(2, 2), bias_grad=0, gemm=0,
                layernorm_fwd=5, layernorm_bwd=5, attention_fwd=2, attention_bwd=2, cast_bf16=1, dropout_apply=0,
                droppath_apply=0, layerscale_fold=0, layerscale_bwd=0)
-VIT_K = _with(BLOCK_K, gemm=26, attn_fwd=2, attn_bwd=2, cast=1, fold=4)
+VIT_K = _with(BLOCK_K, gemm=26, ln_fwd_small=5, ln_bwd_small=5, attn_fwd=2, attn_bwd=2, cast=1, fold=4)
 MLP_OPS = dict(linear_fwd=2, linear_dgrad=2, linear_wgrad=2, wgrad_group=(), bias_grad=1, gemm=0, layernorm_fwd=0,
                layernorm_bwd=0, attention_fwd=0, attention_bwd=0, cast_bf16=4, dropout_apply=0, droppath_apply=0,
                layerscale_fold=0, layerscale_bwd=0)
-MLP_K = _with(BLOCK_K, gemm=6, attn_fwd=0, attn_bwd=0, cast=4)
+MLP_K = _with(BLOCK_K, gemm=6, ln_fwd_small=0, ln_bwd_small=0, attn_fwd=0, attn_bwd=0, cast=4)
 ATTN_OPS = _with(MLP_OPS, attention_fwd=1, attention_bwd=1)
 ATTN_K = _with(MLP_K, attn_fwd=1, attn_bwd=1)
 # CvT, 3 stages of one block, bf16.  Per stage: conv embed (forward GEMM; backward: cast, weight
@@ -241,7 +243,8 @@ ATTN_K = _with(MLP_K, attn_fwd=1, attn_bwd=1)
 CVT_OPS = dict(linear_fwd=12, linear_dgrad=20, linear_wgrad=21, wgrad_group=(), bias_grad=18, gemm=9,
                layernorm_fwd=7, layernorm_bwd=7, attention_fwd=3, attention_bwd=3, cast_bf16=24, dropout_apply=0,
                droppath_apply=0, layerscale_fold=0, layerscale_bwd=0)
-CVT_K = _with(BLOCK_K, gemm=62, splitk_reduce=7, ln_fwd=3, ln_bwd=3, attn_fwd=3, attn_bwd=4, cast=24, fold=34)
+CVT_K = _with(BLOCK_K, gemm=62, splitk_reduce=7, ln_fwd=3, ln_bwd=3, ln_fwd_small=4, ln_bwd_small=4, attn_fwd=3, attn_bwd=4,
+              cast=24, fold=34)
 
 CASES = {
     "block-bf16": (_block(), BLOCK_OPS, BLOCK_K),

@@ -11,7 +11,6 @@ from vitmi import ops  # noqa: E402
 
 DEV = "cuda"
 BF = torch.bfloat16
-E4 = torch.float8_e4m3fn
 
 
 def rnd(*shape, scale=1.0, seed=0):
@@ -19,28 +18,11 @@ def rnd(*shape, scale=1.0, seed=0):
     return torch.randn(*shape, generator=g) * scale
 
 
-def e4m3(x):
-    """fp32 -> e4m3 bytes (saturating at +-448 as the kernels do)."""
-    return x.clamp(-448.0, 448.0).to(E4).view(torch.uint8)
-
-
-def ref_parts(x):
-    """(hi bf16, hi8 bytes, lo8 bytes) of fp32 x on the CPU."""
-    x = x.float().cpu()
-    hi = x.to(BF)
-    return hi, e4m3(hi.float()), e4m3((x - hi.float()) * 512.0)
-
-
-def parts(y8, K):
-    """(hi bf16 [rows, K], first e4m3 part, second e4m3 part) of VITMI_BF16F8 rows [rows, 2K]; the
-    e4m3 part is laid out in 64-k blocks [first | second] (common.h f8_off)."""
-    rows = y8.shape[0]
-    b = y8.contiguous().cpu().view(torch.uint8)[:, 2 * K:].reshape(rows, K // 64, 2, 64)
-    return y8[:, :K].cpu(), b[:, :, 0].reshape(rows, K), b[:, :, 1].reshape(rows, K)
-
-
-def deq(b):
-    return b.view(E4).double()
+# the CPU conversions and the row layout live with the LayerNorm reference, which judges the same rows:
+# ref_parts(x) = (hi bf16, hi8 bytes, lo8 bytes) of fp32 x; parts(y8, K) = (hi, first e4m3 part, second
+# e4m3 part) of VITMI_BF16F8 rows [rows, 2K], the e4m3 part in 64-k blocks [first | second] (common.h
+# f8_off); deq(bytes) = their values
+from ref_layernorm import e4m3, e4m3_value as deq, f8_unpack as parts, split_f8 as ref_parts  # noqa: E402
 
 
 @pytest.mark.parametrize("rows,K", [(197 * 3, 768), (37, 3072), (5, 64)])

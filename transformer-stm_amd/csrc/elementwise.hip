@@ -526,7 +526,12 @@ extern "C" size_t vitmi_bias_grad_workspace_size(int64_t M, int64_t N) {
 
 extern "C" int vitmi_bias_grad(int dtype, int64_t M, int64_t N, const void* dy, int64_t ldy,
                                float* db, void* workspace, size_t ws_bytes, vitmi_stream_t stream) {
+  VITMI_CHECK_ARG(dtype == VITMI_F32 || dtype == VITMI_BF16, "bias_grad: dtype must be VITMI_F32 or VITMI_BF16");
+  VITMI_CHECK_ARG(M >= 0 && N >= 0 && ldy >= N, "bias_grad: ldy >= N required");
   VITMI_CHECK_ARG(dy && db, "bias_grad: null pointer");
+  VITMI_CHECK_ARG((uintptr_t)dy % (dtype == VITMI_BF16 ? 2 : 4) == 0 && (uintptr_t)db % 4 == 0,
+                  "bias_grad: dy and db must be aligned to their element (a 16-byte aligned dy with N %% 8 == 0 and "
+                  "ldy %% 8 == 0 takes the vector kernel)");
   VITMI_CHECK_ARG(workspace && ws_bytes >= vitmi_bias_grad_workspace_size(M, N), "bias_grad: workspace too small");
   if (M == 0 || N == 0) return VITMI_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -548,12 +553,15 @@ extern "C" int vitmi_bias_grad(int dtype, int64_t M, int64_t N, const void* dy, 
     }
   } else {
     dim3 grid((unsigned)((N + 255) / 256), Z);
-    if (dtype == VITMI_BF16)
+    if (dtype == VITMI_BF16) {
       hipLaunchKernelGGL(colsum_kernel<bf16>, grid, dim3(256), 0, s, M, N, (const bf16*)dy, ldy,
                          (float*)workspace, rows_per);
-    else
+      VITMI_STAT(colsum_kernel<bf16>, 0, (double)M * N * 2);
+    } else {
       hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, s, M, N, (const float*)dy, ldy,
                          (float*)workspace, rows_per);
+      VITMI_STAT(colsum_kernel<float>, 0, (double)M * N * 4);
+    }
   }
   VITMI_LAUNCH_CHECK("bias_grad");
   return fold_rows((const float*)workspace, Z, N, N, db, s);

@@ -307,6 +307,9 @@ __global__ __launch_bounds__(256) void ln_bwd_small_kernel(
   }
 }
 
+// a null pointer (an output that is not asked for) counts as aligned
+static bool aligned_to(const void* p, uintptr_t bytes) { return (uintptr_t)p % bytes == 0; }
+
 static constexpr int LN_BWD_BLOCKS = 512;
 static int ln_blocks_bwd(int64_t M) {
   int64_t g = (M + 3) / 4;
@@ -388,26 +391,29 @@ extern "C" int vitmi_layernorm_fwd(int64_t M, int D, const float* x, int64_t ldx
   VITMI_CHECK_ARG(y_dtype != VITMI_BF16F8W || D % 128 == 0, "layernorm_fwd: VITMI_BF16F8W needs D %% 128 == 0");
   if (M == 0) return VITMI_OK;
   VITMI_CHECK_ARG(x && gamma && beta && y && mean && rstd, "layernorm_fwd: null pointer");
+  VITMI_CHECK_ARG(aligned_to(x, 16) && aligned_to(gamma, 16) && aligned_to(beta, 16) &&
+                      aligned_to(y, y_dtype == VITMI_F32 ? 16 : 8),
+                  "layernorm_fwd: x, gamma, beta and an fp32 y must be 16-byte aligned, a bf16 y 8-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   if ((D == 64 || D == 128) && y_dtype != VITMI_BF16X3 && y_dtype != VITMI_BF16F8 &&
       y_dtype != VITMI_BF16F8W) {
     const int rw = 64 / (D / 4);
     const dim3 grid((unsigned)((M + 4 * rw - 1) / (4 * rw)));
+    // x (fp32) read, y written, mean/rstd written: the byte formula of ln_fwd_launch
+#define LNF(LL, TY)                                                                                          \
+  do {                                                                                                       \
+    hipLaunchKernelGGL((ln_fwd_small_kernel<LL, TY>), grid, dim3(256), 0, s, M, x, ldx, gamma, beta, eps,    \
+                       (TY*)y, ldy, mean, rstd);                                                             \
+    VITMI_STAT((ln_fwd_small_kernel<LL, TY>), 0, (double)M * D * (4 + sizeof(TY)) + 8.0 * M);                \
+  } while (0)
     if (D == 64) {
-      if (y_dtype == VITMI_BF16)
-        hipLaunchKernelGGL((ln_fwd_small_kernel<16, bf16>), grid, dim3(256), 0, s, M, x, ldx, gamma, beta, eps,
-                           (bf16*)y, ldy, mean, rstd);
-      else
-        hipLaunchKernelGGL((ln_fwd_small_kernel<16, float>), grid, dim3(256), 0, s, M, x, ldx, gamma, beta, eps,
-                           (float*)y, ldy, mean, rstd);
+      if (y_dtype == VITMI_BF16) LNF(16, bf16);
+      else LNF(16, float);
     } else {
-      if (y_dtype == VITMI_BF16)
-        hipLaunchKernelGGL((ln_fwd_small_kernel<32, bf16>), grid, dim3(256), 0, s, M, x, ldx, gamma, beta, eps,
-                           (bf16*)y, ldy, mean, rstd);
-      else
-        hipLaunchKernelGGL((ln_fwd_small_kernel<32, float>), grid, dim3(256), 0, s, M, x, ldx, gamma, beta, eps,
-                           (float*)y, ldy, mean, rstd);
+      if (y_dtype == VITMI_BF16) LNF(32, bf16);
+      else LNF(32, float);
     }
+#undef LNF
     VITMI_LAUNCH_CHECK("layernorm_fwd");
     return VITMI_OK;
   }
@@ -434,8 +440,18 @@ extern "C" int vitmi_layernorm_bwd(int64_t M, int D, const void* dy, int dy_dtyp
                                    int64_t lddx_lp, float* dgamma, float* dbeta, float* dxsum,
                                    void* workspace, size_t ws_bytes, vitmi_stream_t stream) {
   VITMI_CHECK_ARG(D > 0 && D % 4 == 0 && D <= 2048, "layernorm: D must be a multiple of 4 in [4, 2048]");
+  VITMI_CHECK_ARG(dy_dtype == VITMI_F32 || dy_dtype == VITMI_BF16, "layernorm_bwd: dy dtype must be VITMI_F32 or VITMI_BF16");
+  VITMI_CHECK_ARG(lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 && (!dres || ldres % 4 == 0) &&
+                      (!dx_lp || lddx_lp % 4 == 0),
+                  "layernorm_bwd: strides must be multiples of 4");
+  VITMI_CHECK_ARG(lddy >= D && ldx >= D && lddx >= D && (!dres || ldres >= D) && (!dx_lp || lddx_lp >= D),
+                  "layernorm_bwd: lddy, ldx, lddx (and ldres, lddx_lp of a given dres, dx_lp) >= D required");
   if (M == 0) return VITMI_OK;
   VITMI_CHECK_ARG(dy && x && mean && rstd && gamma && dx, "layernorm_bwd: null pointer");
+  VITMI_CHECK_ARG(aligned_to(dy, dy_dtype == VITMI_BF16 ? 8 : 16) && aligned_to(x, 16) && aligned_to(gamma, 16) &&
+                      aligned_to(dres, 16) && aligned_to(dx, 16) && aligned_to(dx_lp, 8),
+                  "layernorm_bwd: x, gamma, dres, dx and an fp32 dy must be 16-byte aligned, a bf16 dy and dx_lp "
+                  "8-byte aligned");
   VITMI_CHECK_ARG(workspace && ws_bytes >= vitmi_layernorm_bwd_workspace_size(M, D),
                   "layernorm_bwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
@@ -443,9 +459,14 @@ extern "C" int vitmi_layernorm_bwd(int64_t M, int D, const void* dy, int dy_dtyp
   float* part = (float*)workspace;
   const int nv = (D + 255) / 256;
   if (D == 64 || D == 128) {
-#define LNS(LL, TD, LPB)                                                                          \
-  hipLaunchKernelGGL((ln_bwd_small_kernel<LL, TD, LPB>), dim3(G), dim3(256), 0, s, M, (const TD*)dy, lddy, x, ldx, \
-                     mean, rstd, gamma, dres, ldres, dx, lddx, (bf16*)dx_lp, lddx_lp, part)
+    // dy + x (+ dres) read, dx (+ bf16 copy) written: the byte formula of ln_bwd_launch
+#define LNS(LL, TD, LPB)                                                                                              \
+  do {                                                                                                                \
+    hipLaunchKernelGGL((ln_bwd_small_kernel<LL, TD, LPB>), dim3(G), dim3(256), 0, s, M, (const TD*)dy, lddy, x, ldx,  \
+                       mean, rstd, gamma, dres, ldres, dx, lddx, (bf16*)dx_lp, lddx_lp, part);                        \
+    VITMI_STAT((ln_bwd_small_kernel<LL, TD, LPB>), 0,                                                                 \
+               (double)M * D * (sizeof(TD) + 4 + (dres ? 4 : 0) + 4 + (LPB ? 2 : 0)) + 8.0 * M);                      \
+  } while (0)
     const bool bf = dy_dtype == VITMI_BF16, lp = dx_lp != nullptr;
     if (D == 64) {
       if (bf) { if (lp) LNS(16, bf16, true); else LNS(16, bf16, false); }
