@@ -60,6 +60,19 @@ void stat_record(const void* kernel, double flops, double bytes) {
   g_stats[i].bytes += bytes;
 }
 
+// compute units of the current device (the persistent grids of gemm.hip and attention.hip), looked up
+// once; 256 (the MI355X) when the query fails
+int device_cus() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
+      return n;
+    return 256;
+  }();
+  return cus;
+}
+
 }  // namespace vitmi
 
 extern "C" int vitmi_stats_enable(int on) {

@@ -2212,26 +2212,6 @@ static AttnPlan attn_plan(int dtype, int N) {
 // the largest colsum_rows over all policies (the policy may change between a workspace query and the call)
 static int attn_colsum_rows_max(int N) { return (N + 127) / 128; }
 
-// one launch and its VITMI_STAT record, both from the same kernel symbol
-template <typename... P, typename... A>
-static void launch(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t s, double flops, double bytes, A... args) {
-  hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
-  VITMI_STAT(kernel, flops, bytes);
-}
-
-static int device_cus() {   // compute units of the current device (the persistent backward grids)
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      cus = n;
-    else
-      cus = 256;
-  }
-  return cus;
-}
-
 extern "C" int vitmi_attention_set_policy(int policy) {
   VITMI_CHECK_ARG(policy >= 0 && policy <= 3, "attention_set_policy: policy must be 0..3");
   const int prev = g_attn_policy;
@@ -2344,15 +2324,11 @@ static int attention_bwd_impl(int dtype, int B, int N, int H, int dh, float scal
   const int npairs = B * H;
   const dim3 pairs(npairs), cus(npairs < device_cus() ? npairs : device_cus()), waves(64 * p.nkb);
   if (p.path == SEQ_BF16 && p.fused) {
-    switch (p.nkb) {   // <= FUSED_NKB
-#define FUSED(NKB)                                                                                             \
-  case NKB:                                                                                                    \
-    launch(attn_bwd_fused_seq_bf16<NKB>, cus, waves, s, 2 * fl, t * 8 * 2 + bh * N * 8, q16, o16, do16, lse, delta, \
-           (bf16*)dqkv, N, H, scale, colsum, npairs);                                                          \
-    break
-      FUSED(1); FUSED(2); FUSED(3); FUSED(4); FUSED(5); FUSED(6); FUSED(7);
-#undef FUSED
-    }
+    static constexpr decltype(&attn_bwd_fused_seq_bf16<1>) fused[FUSED_NKB] = {
+        attn_bwd_fused_seq_bf16<1>, attn_bwd_fused_seq_bf16<2>, attn_bwd_fused_seq_bf16<3>, attn_bwd_fused_seq_bf16<4>,
+        attn_bwd_fused_seq_bf16<5>, attn_bwd_fused_seq_bf16<6>, attn_bwd_fused_seq_bf16<7>};
+    launch(fused[p.nkb - 1], cus, waves, s, 2 * fl, t * 8 * 2 + bh * N * 8, q16, o16, do16, lse, delta, (bf16*)dqkv, N,
+           H, scale, colsum, npairs);
   } else if (p.path == SEQ_BF16) {
     // dQ first: it also writes delta, which the dK/dV kernel consumes
     const auto run = [&](auto dq, dim3 dq_block, auto dkv) {
@@ -2380,12 +2356,12 @@ static int attention_bwd_impl(int dtype, int B, int N, int H, int dh, float scal
   } else {
     // (the streamed fp32 backward records no work)
     const dim3 grid((N + 63) / 64, B * H);
-    hipLaunchKernelGGL(attn_bwd_delta<float>, dim3((unsigned)(((int64_t)B * N * H + 255) / 256)), dim3(256), 0, s, o32,
-                       do32, delta, B * N, N, H);
-    hipLaunchKernelGGL(attn_bwd_dkv_f32, grid, dim3(256), 0, s, q32, do32, lse, (const float*)delta, (float*)dqkv, N,
-                       H, scale);
-    hipLaunchKernelGGL(attn_bwd_dq_f32, grid, dim3(256), 0, s, q32, do32, lse, (const float*)delta, (float*)dqkv, N,
-                       H, scale);
+    launch(attn_bwd_delta<float>, dim3((unsigned)(((int64_t)B * N * H + 255) / 256)), dim3(256), s, no_stat, o32, do32,
+           delta, B * N, N, H);
+    launch(attn_bwd_dkv_f32, grid, dim3(256), s, no_stat, q32, do32, lse, (const float*)delta, (float*)dqkv, N, H,
+           scale);
+    launch(attn_bwd_dq_f32, grid, dim3(256), s, no_stat, q32, do32, lse, (const float*)delta, (float*)dqkv, N, H,
+           scale);
   }
   VITMI_LAUNCH_CHECK("attention_bwd");
   if (colsum_rows && colsum) *colsum_rows = B * p.colsum_rows;

@@ -17,65 +17,69 @@ struct PatchGeom {
   int64_t np, rows, K;
 };
 
-int patch_geom(int B, int C, int S, int P, int D, PatchGeom& g) {
+// keep: the patch-dropout form (csrc/patchdrop.hip), the same composition over rows = B * keep_n
+// gathered rows; the patch GEMM runs at M = B * keep_n
+int patch_geom(int B, int C, int S, int P, int D, bool keep, int keep_n, PatchGeom& g) {
   VITMI_CHECK_ARG(B > 0 && C > 0 && D > 0 && P > 0 && S % P == 0, "patch_embed: bad shape");
   VITMI_CHECK_ARG(D % 4 == 0, "patch_embed: D %% 4 != 0");
   g.np = (int64_t)(S / P) * (S / P);
   g.rows = (int64_t)B * g.np;
   g.K = (int64_t)C * P * P;
+  if (keep) {
+    VITMI_CHECK_ARG(keep_n >= 1 && keep_n <= g.np && g.np <= 4096, "patch_embed_keep: need 1 <= K <= np <= 4096");
+    g.rows = (int64_t)B * keep_n;
+  }
   return VITMI_OK;
 }
 
 int es_of(int dtype) { return dtype == VITMI_BF16 ? 2 : 4; }
 
-}  // namespace
-
-// ---- patch embedding: Conv2D(D, k=P, s=P) + cls + pos (models/CvT(Par).py:203-212,244-245)
-extern "C" size_t vitmi_patch_embed_fwd_workspace_size(int dtype, int B, int C, int S, int P, int D) {
-  PatchGeom g;
-  if (patch_geom(B, C, S, P, D, g)) return 0;
+// conv (fp32 [rows, D]), then the patch GEMM's workspace
+size_t embed_fwd_ws(int dtype, const PatchGeom& g, int D) {
   return align_up((size_t)g.rows * D * sizeof(float)) + vitmi_linear_fwd_workspace_size(dtype, g.rows, D, g.K);
 }
 
-extern "C" int vitmi_patch_embed_fwd(int dtype, int B, int C, int S, int P, int D, const float* img, const void* w,
-                                     const float* bias, const float* cls, const float* pos, void* patches, float* x,
-                                     void* workspace, size_t ws_bytes, vitmi_stream_t stream) {
-  PatchGeom g;
-  if (int rc = patch_geom(B, C, S, P, D, g)) return rc;
-  VITMI_CHECK_ARG(img && w && patches && x, "patch_embed_fwd: null pointer");
-  const size_t need = vitmi_patch_embed_fwd_workspace_size(dtype, B, C, S, P, D);
-  VITMI_CHECK_ARG(workspace && ws_bytes >= need, "patch_embed_fwd: workspace %zu < %zu bytes", ws_bytes, need);
-  float* conv = (float*)workspace;
-  char* lin_ws = (char*)workspace + align_up((size_t)g.rows * D * sizeof(float));
-  if (int rc = vitmi_patch_im2col(dtype, B, C, S, P, img, patches, stream)) return rc;
-  if (int rc = vitmi_linear_fwd(dtype, g.rows, D, g.K, patches, w, bias, conv, VITMI_F32, VITMI_EPI_STORE, nullptr,
-                                nullptr, lin_ws, ws_bytes - (lin_ws - (char*)workspace), stream))
-    return rc;
-  return vitmi_tokens_assemble(B, (int)g.np, D, conv, cls, pos, x, stream);
-}
-
-extern "C" size_t vitmi_patch_embed_bwd_workspace_size(int dtype, int B, int C, int S, int P, int D) {
-  PatchGeom g;
-  if (patch_geom(B, C, S, P, D, g)) return 0;
+// dtok ([rows, D] in the GEMM dtype), then the larger of the weight- and bias-gradient workspaces
+size_t embed_bwd_ws(int dtype, const PatchGeom& g, int D) {
   const size_t wg = vitmi_linear_wgrad_workspace_size(dtype, g.rows, D, g.K);
   const size_t bg = vitmi_bias_grad_workspace_size(g.rows, D);
   return align_up((size_t)g.rows * D * es_of(dtype)) + (wg > bg ? wg : bg);
 }
 
-extern "C" int vitmi_patch_embed_bwd(int dtype, int B, int C, int S, int P, int D, const float* dx,
-                                     const void* patches, float* dw, float* dbias, float* dcls, float* dpos,
-                                     void* workspace, size_t ws_bytes, vitmi_stream_t stream) {
-  PatchGeom g;
-  if (int rc = patch_geom(B, C, S, P, D, g)) return rc;
-  VITMI_CHECK_ARG(dx && patches, "patch_embed_bwd: null pointer");
-  const size_t need = vitmi_patch_embed_bwd_workspace_size(dtype, B, C, S, P, D);
-  VITMI_CHECK_ARG(workspace && ws_bytes >= need, "patch_embed_bwd: workspace %zu < %zu bytes", ws_bytes, need);
+// The forward of vitmi_patch_embed_fwd (keep == nullptr) and vitmi_patch_embed_keep_fwd, past their
+// geometry and null-pointer checks; `what` is the entry point's name in the refusal.
+int embed_fwd(const char* what, const PatchGeom& g, int dtype, int B, int C, int S, int P, int D, int keep_n,
+              const int32_t* keep, const float* img, const void* w, const float* bias, const float* cls,
+              const float* pos, void* patches, float* x, void* workspace, size_t ws_bytes, vitmi_stream_t stream) {
+  const size_t need = embed_fwd_ws(dtype, g, D);
+  VITMI_CHECK_ARG(workspace && ws_bytes >= need, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
+  float* conv = (float*)workspace;
+  char* lin_ws = (char*)workspace + align_up((size_t)g.rows * D * sizeof(float));
+  if (int rc = keep ? vitmi_patch_im2col_keep(dtype, B, C, S, P, keep_n, keep, img, patches, stream)
+                    : vitmi_patch_im2col(dtype, B, C, S, P, img, patches, stream))
+    return rc;
+  if (int rc = vitmi_linear_fwd(dtype, g.rows, D, g.K, patches, w, bias, conv, VITMI_F32, VITMI_EPI_STORE, nullptr,
+                                nullptr, lin_ws, ws_bytes - (lin_ws - (char*)workspace), stream))
+    return rc;
+  return keep ? vitmi_tokens_assemble_keep(B, (int)g.np, keep_n, D, conv, cls, pos, keep, x, stream)
+              : vitmi_tokens_assemble(B, (int)g.np, D, conv, cls, pos, x, stream);
+}
+
+// The backward of vitmi_patch_embed_bwd (slot == nullptr) and vitmi_patch_embed_keep_bwd, likewise.
+int embed_bwd(const char* what, const PatchGeom& g, int dtype, int B, int D, int keep_n, const int32_t* slot,
+              const float* dx, const void* patches, float* dw, float* dbias, float* dcls, float* dpos, void* workspace,
+              size_t ws_bytes, vitmi_stream_t stream) {
+  const size_t need = embed_bwd_ws(dtype, g, D);
+  VITMI_CHECK_ARG(workspace && ws_bytes >= need, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
   void* dtok = workspace;
   char* rest = (char*)workspace + align_up((size_t)g.rows * D * es_of(dtype));
   const size_t rest_bytes = ws_bytes - (rest - (char*)workspace);
   const bool lp = dtype == VITMI_BF16;
-  if (int rc = vitmi_tokens_assemble_bwd(B, (int)g.np, D, dx, lp ? nullptr : (float*)dtok, lp ? dtok : nullptr, dcls,
-                                         dpos, stream))
+  float* dtok32 = lp ? nullptr : (float*)dtok;
+  void* dtok16 = lp ? dtok : nullptr;
+  if (int rc = slot ? vitmi_tokens_assemble_keep_bwd(B, (int)g.np, keep_n, D, dx, dtok32, dtok16, dcls, dpos, slot,
+                                                     stream)
+                    : vitmi_tokens_assemble_bwd(B, (int)g.np, D, dx, dtok32, dtok16, dcls, dpos, stream))
     return rc;
   if (dw)
     if (int rc = vitmi_linear_wgrad(dtype, g.rows, D, g.K, dtok, patches, dw, rest, rest_bytes, stream)) return rc;
@@ -84,21 +88,38 @@ extern "C" int vitmi_patch_embed_bwd(int dtype, int B, int C, int S, int P, int 
   return VITMI_OK;
 }
 
-// ---- patch embedding of the kept patches only (patch dropout, csrc/patchdrop.hip): the same
-// composition over rows = B*keep_n gathered rows; the patch GEMM runs at M = B*keep_n
-namespace {
-int keep_geom(int B, int C, int S, int P, int D, int keep_n, PatchGeom& g) {
-  if (int rc = patch_geom(B, C, S, P, D, g)) return rc;
-  VITMI_CHECK_ARG(keep_n >= 1 && keep_n <= g.np && g.np <= 4096, "patch_embed_keep: need 1 <= K <= np <= 4096");
-  g.rows = (int64_t)B * keep_n;
-  return VITMI_OK;
-}
 }  // namespace
+
+// ---- patch embedding: Conv2D(D, k=P, s=P) + cls + pos (models/CvT(Par).py:203-212,244-245), and
+// the same over the kept patches only (patch dropout)
+extern "C" size_t vitmi_patch_embed_fwd_workspace_size(int dtype, int B, int C, int S, int P, int D) {
+  PatchGeom g;
+  return patch_geom(B, C, S, P, D, false, 0, g) ? 0 : embed_fwd_ws(dtype, g, D);
+}
 
 extern "C" size_t vitmi_patch_embed_keep_fwd_workspace_size(int dtype, int B, int C, int S, int P, int D, int K) {
   PatchGeom g;
-  if (keep_geom(B, C, S, P, D, K, g)) return 0;
-  return align_up((size_t)g.rows * D * sizeof(float)) + vitmi_linear_fwd_workspace_size(dtype, g.rows, D, g.K);
+  return patch_geom(B, C, S, P, D, true, K, g) ? 0 : embed_fwd_ws(dtype, g, D);
+}
+
+extern "C" size_t vitmi_patch_embed_bwd_workspace_size(int dtype, int B, int C, int S, int P, int D) {
+  PatchGeom g;
+  return patch_geom(B, C, S, P, D, false, 0, g) ? 0 : embed_bwd_ws(dtype, g, D);
+}
+
+extern "C" size_t vitmi_patch_embed_keep_bwd_workspace_size(int dtype, int B, int C, int S, int P, int D, int K) {
+  PatchGeom g;
+  return patch_geom(B, C, S, P, D, true, K, g) ? 0 : embed_bwd_ws(dtype, g, D);
+}
+
+extern "C" int vitmi_patch_embed_fwd(int dtype, int B, int C, int S, int P, int D, const float* img, const void* w,
+                                     const float* bias, const float* cls, const float* pos, void* patches, float* x,
+                                     void* workspace, size_t ws_bytes, vitmi_stream_t stream) {
+  PatchGeom g;
+  if (int rc = patch_geom(B, C, S, P, D, false, 0, g)) return rc;
+  VITMI_CHECK_ARG(img && w && patches && x, "patch_embed_fwd: null pointer");
+  return embed_fwd("patch_embed_fwd", g, dtype, B, C, S, P, D, 0, nullptr, img, w, bias, cls, pos, patches, x,
+                   workspace, ws_bytes, stream);
 }
 
 extern "C" int vitmi_patch_embed_keep_fwd(int dtype, int B, int C, int S, int P, int D, int K, const int32_t* keep,
@@ -106,25 +127,20 @@ extern "C" int vitmi_patch_embed_keep_fwd(int dtype, int B, int C, int S, int P,
                                           const float* pos, void* patches, float* x, void* workspace,
                                           size_t ws_bytes, vitmi_stream_t stream) {
   PatchGeom g;
-  if (int rc = keep_geom(B, C, S, P, D, K, g)) return rc;
+  if (int rc = patch_geom(B, C, S, P, D, true, K, g)) return rc;
   VITMI_CHECK_ARG(keep && img && w && patches && x, "patch_embed_keep_fwd: null pointer");
-  const size_t need = vitmi_patch_embed_keep_fwd_workspace_size(dtype, B, C, S, P, D, K);
-  VITMI_CHECK_ARG(workspace && ws_bytes >= need, "patch_embed_keep_fwd: workspace %zu < %zu bytes", ws_bytes, need);
-  float* conv = (float*)workspace;
-  char* lin_ws = (char*)workspace + align_up((size_t)g.rows * D * sizeof(float));
-  if (int rc = vitmi_patch_im2col_keep(dtype, B, C, S, P, K, keep, img, patches, stream)) return rc;
-  if (int rc = vitmi_linear_fwd(dtype, g.rows, D, g.K, patches, w, bias, conv, VITMI_F32, VITMI_EPI_STORE, nullptr,
-                                nullptr, lin_ws, ws_bytes - (lin_ws - (char*)workspace), stream))
-    return rc;
-  return vitmi_tokens_assemble_keep(B, (int)g.np, K, D, conv, cls, pos, keep, x, stream);
+  return embed_fwd("patch_embed_keep_fwd", g, dtype, B, C, S, P, D, K, keep, img, w, bias, cls, pos, patches, x,
+                   workspace, ws_bytes, stream);
 }
 
-extern "C" size_t vitmi_patch_embed_keep_bwd_workspace_size(int dtype, int B, int C, int S, int P, int D, int K) {
+extern "C" int vitmi_patch_embed_bwd(int dtype, int B, int C, int S, int P, int D, const float* dx,
+                                     const void* patches, float* dw, float* dbias, float* dcls, float* dpos,
+                                     void* workspace, size_t ws_bytes, vitmi_stream_t stream) {
   PatchGeom g;
-  if (keep_geom(B, C, S, P, D, K, g)) return 0;
-  const size_t wg = vitmi_linear_wgrad_workspace_size(dtype, g.rows, D, g.K);
-  const size_t bg = vitmi_bias_grad_workspace_size(g.rows, D);
-  return align_up((size_t)g.rows * D * es_of(dtype)) + (wg > bg ? wg : bg);
+  if (int rc = patch_geom(B, C, S, P, D, false, 0, g)) return rc;
+  VITMI_CHECK_ARG(dx && patches, "patch_embed_bwd: null pointer");
+  return embed_bwd("patch_embed_bwd", g, dtype, B, D, 0, nullptr, dx, patches, dw, dbias, dcls, dpos, workspace,
+                   ws_bytes, stream);
 }
 
 extern "C" int vitmi_patch_embed_keep_bwd(int dtype, int B, int C, int S, int P, int D, int K, const int32_t* slot,
@@ -132,22 +148,10 @@ extern "C" int vitmi_patch_embed_keep_bwd(int dtype, int B, int C, int S, int P,
                                           float* dcls, float* dpos, void* workspace, size_t ws_bytes,
                                           vitmi_stream_t stream) {
   PatchGeom g;
-  if (int rc = keep_geom(B, C, S, P, D, K, g)) return rc;
+  if (int rc = patch_geom(B, C, S, P, D, true, K, g)) return rc;
   VITMI_CHECK_ARG(slot && dx && patches, "patch_embed_keep_bwd: null pointer");
-  const size_t need = vitmi_patch_embed_keep_bwd_workspace_size(dtype, B, C, S, P, D, K);
-  VITMI_CHECK_ARG(workspace && ws_bytes >= need, "patch_embed_keep_bwd: workspace %zu < %zu bytes", ws_bytes, need);
-  void* dtok = workspace;
-  char* rest = (char*)workspace + align_up((size_t)g.rows * D * es_of(dtype));
-  const size_t rest_bytes = ws_bytes - (rest - (char*)workspace);
-  const bool lp = dtype == VITMI_BF16;
-  if (int rc = vitmi_tokens_assemble_keep_bwd(B, (int)g.np, K, D, dx, lp ? nullptr : (float*)dtok,
-                                              lp ? dtok : nullptr, dcls, dpos, slot, stream))
-    return rc;
-  if (dw)
-    if (int rc = vitmi_linear_wgrad(dtype, g.rows, D, g.K, dtok, patches, dw, rest, rest_bytes, stream)) return rc;
-  if (dbias)
-    if (int rc = vitmi_bias_grad(dtype, g.rows, D, dtok, D, dbias, rest, rest_bytes, stream)) return rc;
-  return VITMI_OK;
+  return embed_bwd("patch_embed_keep_bwd", g, dtype, B, D, K, slot, dx, patches, dw, dbias, dcls, dpos, workspace,
+                   ws_bytes, stream);
 }
 
 // ---- Dense backward: dx = dy W, dW += dy^T x, db += colsum(dy)  (autodiff of layers.Dense)

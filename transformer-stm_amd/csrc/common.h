@@ -173,6 +173,49 @@ void stat_record(const void* kernel, double flops, double bytes);
     if (::vitmi::g_stats_on) ::vitmi::stat_record((const void*)(kernel), (double)(flops), (double)(bytes)); \
   } while (0)
 
+// ---------------------------------------------------------------- host launch layer
+// Every kernel launch of the library: one hipLaunchKernelGGL and its VITMI_STAT record, both from the
+// same kernel argument.  A kernel that records no work is launched with `no_stat` in place of the flops
+// and bytes.  Neither form checks the launch: VITMI_LAUNCH_CHECK returns from its caller, so it stays
+// in the entry point.
+template <typename... P, typename... A>
+inline void launch(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t s, double flops, double bytes, A... args) {
+  hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
+  VITMI_STAT(kernel, flops, bytes);
+}
+struct NoStat {};
+constexpr NoStat no_stat{};
+template <typename... P, typename... A>
+inline void launch(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t s, NoStat, A... args) {
+  hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
+}
+
+// A kernel seen with untyped pointer parameters, so that the instances of one template that differ
+// in an operand's element type share one pointer type: a runtime dtype picks the instance (a
+// conditional expression or a small table), then one launch takes it.  Only the pointee types are
+// erased; the launch packs the same arguments.
+template <typename T> struct untyped_param { typedef T type; };
+template <typename T> struct untyped_param<T*> { typedef void* type; };
+template <typename T> struct untyped_param<const T*> { typedef const void* type; };
+template <typename... P>
+inline auto untyped(void (*kernel)(P...)) {
+  return reinterpret_cast<void (*)(typename untyped_param<P>::type...)>(kernel);
+}
+
+// blocks of a grid-stride launch: ceil(work / per_block) in [1, cap]; GRID_NO_CAP (the grid's own
+// limit) for a kernel that takes one block per per_block items, whatever the work
+constexpr int64_t GRID_NO_CAP = 0x7fffffff;
+inline unsigned grid_cap(int64_t work, int per_block = 256, int64_t cap = 8192) {
+  const int64_t g = (work + per_block - 1) / per_block;
+  return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
+}
+
+// a null pointer (an output that is not asked for) counts as aligned
+inline bool aligned_to(const void* p, uintptr_t bytes) { return (uintptr_t)p % bytes == 0; }
+
+// compute units of the current device, looked up once; 256 (the MI355X) when the query fails (abi.cpp)
+int device_cus();
+
 // db[n] += sum_z part[z][n] in a fixed order (elementwise.hip)
 int launch_colsum_finish(int64_t N, int Z, const float* part, float* db, hipStream_t s);
 // out[c] += sum_r part[r * ld + c] (fixed order), launched now or, between vitmi_fold_begin and

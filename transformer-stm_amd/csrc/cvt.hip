@@ -456,11 +456,7 @@ __global__ __launch_bounds__(1024) void dw_wgrad_finalize_kernel(const float* __
   if (threadIdx.x < RED_COLS && ok) dwt[e] += (float)s;
 }
 
-static unsigned grid_of(int64_t work, int per_block = 256, int cap = 4096) {
-  int64_t gsz = (work + per_block - 1) / per_block;
-  if (gsz > cap) gsz = cap;
-  return (unsigned)(gsz < 1 ? 1 : gsz);
-}
+static constexpr int64_t CVT_BLOCKS = 4096;   // grid_cap's cap for the grid-stride kernels of this file
 
 static int dw_blocks(int64_t n, int C) {
   const int lanes = 256 / (C / 4);
@@ -516,16 +512,11 @@ extern "C" int vitmi_conv_im2col(int dtype, int B, int H, int W, int C, int kh, 
   VITMI_CHECK_ARG(x && patches, "conv_im2col: null pointer");
   VITMI_CHECK_ARG(Kp >= kh * kw * C, "conv_im2col: Kp < kh*kw*C");
   VITMI_CHECK_ARG(dtype == VITMI_BF16 || dtype == VITMI_F32, "conv_im2col: bad dtype");
-  const bool vec = C % 4 == 0 && Kp % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)x % 16) == 0;
+  const bool vec = C % 4 == 0 && Kp % 4 == 0 && ldx % 4 == 0 && aligned_to(x, 16), bf = dtype == VITMI_BF16;
   const int64_t work = (int64_t)B * g.Ho * g.Wo * Kp / (vec ? 4 : 1);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == VITMI_BF16) {
-    if (vec) hipLaunchKernelGGL((conv_im2col_kernel<bf16, 4>), dim3(grid_of(work)), dim3(256), 0, st, g, x, (bf16*)patches, Kp);
-    else hipLaunchKernelGGL((conv_im2col_kernel<bf16, 1>), dim3(grid_of(work)), dim3(256), 0, st, g, x, (bf16*)patches, Kp);
-  } else {
-    if (vec) hipLaunchKernelGGL((conv_im2col_kernel<float, 4>), dim3(grid_of(work)), dim3(256), 0, st, g, x, (float*)patches, Kp);
-    else hipLaunchKernelGGL((conv_im2col_kernel<float, 1>), dim3(grid_of(work)), dim3(256), 0, st, g, x, (float*)patches, Kp);
-  }
+  const auto kern = bf ? (vec ? untyped(conv_im2col_kernel<bf16, 4>) : untyped(conv_im2col_kernel<bf16, 1>))
+                       : (vec ? untyped(conv_im2col_kernel<float, 4>) : untyped(conv_im2col_kernel<float, 1>));
+  launch(kern, dim3(grid_cap(work, 256, CVT_BLOCKS)), dim3(256), (hipStream_t)stream, no_stat, g, x, patches, Kp);
   VITMI_LAUNCH_CHECK("conv_im2col");
   return VITMI_OK;
 }
@@ -538,13 +529,9 @@ extern "C" int vitmi_conv_col2im(int dtype, int B, int H, int W, int C, int kh, 
   VITMI_CHECK_ARG(dpatches && dx, "conv_col2im: null pointer");
   VITMI_CHECK_ARG(C % 4 == 0 && ldx % 4 == 0 && Kp >= kh * kw * C, "conv_col2im: C %% 4 == 0 required");
   const int64_t work = (int64_t)B * H * W * (C / 4);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == VITMI_BF16)
-    hipLaunchKernelGGL(conv_col2im_kernel<bf16>, dim3(grid_of(work)), dim3(256), 0, st, g, (const bf16*)dpatches, Kp,
-                       dx, accumulate);
-  else
-    hipLaunchKernelGGL(conv_col2im_kernel<float>, dim3(grid_of(work)), dim3(256), 0, st, g, (const float*)dpatches,
-                       Kp, dx, accumulate);
+  launch(dtype == VITMI_BF16 ? untyped(conv_col2im_kernel<bf16>) : untyped(conv_col2im_kernel<float>),
+         dim3(grid_cap(work, 256, CVT_BLOCKS)), dim3(256), (hipStream_t)stream, no_stat, g, dpatches, Kp, dx,
+         accumulate);
   VITMI_LAUNCH_CHECK("conv_col2im");
   return VITMI_OK;
 }
@@ -583,16 +570,12 @@ extern "C" int vitmi_dwconv_bn_fwd(int B, int H, int W, int C, const float* x, i
   // (the workspace's partial rows)
   int G = (int)(((int64_t)B * H * (C / 4) + 255) / 256);
   if (G > dw_blocks(n, C)) G = dw_blocks(n, C);
-  hipLaunchKernelGGL(dw_fwd_stats_rows_kernel, dim3(G), dim3(256), 0, st, g, x, wt, z, part);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + RED_COLS - 1) / RED_COLS), dim3(1024), 0, st, (const float*)part, G, C, n, eps,
-                     momentum, mean, rstd, run_mean, run_var, training);
-  const int64_t work = n * (C / 4);
-  if (y_dtype == VITMI_BF16)
-    hipLaunchKernelGGL(bn_apply_kernel<bf16>, dim3(grid_of(work)), dim3(256), 0, st, g, (const float*)z,
-                       (const float*)mean, (const float*)rstd, gamma, beta, (bf16*)y, ldy, y_img, y_off);
-  else
-    hipLaunchKernelGGL(bn_apply_kernel<float>, dim3(grid_of(work)), dim3(256), 0, st, g, (const float*)z,
-                       (const float*)mean, (const float*)rstd, gamma, beta, (float*)y, ldy, y_img, y_off);
+  launch(dw_fwd_stats_rows_kernel, dim3(G), dim3(256), st, no_stat, g, x, wt, z, part);
+  launch(bn_finalize_kernel, dim3((C + RED_COLS - 1) / RED_COLS), dim3(1024), st, no_stat, (const float*)part, G, C, n,
+         eps, momentum, mean, rstd, run_mean, run_var, training);
+  launch(y_dtype == VITMI_BF16 ? untyped(bn_apply_kernel<bf16>) : untyped(bn_apply_kernel<float>),
+         dim3(grid_cap(n * (C / 4), 256, CVT_BLOCKS)), dim3(256), st, no_stat, g, z, mean, rstd, gamma, beta, y, ldy,
+         y_img, y_off);
   VITMI_LAUNCH_CHECK("dwconv_bn_fwd");
   return VITMI_OK;
 }
@@ -613,27 +596,19 @@ extern "C" int vitmi_dwconv_bn_bwd(int B, int H, int W, int C, const void* dy, i
   float* part = (float*)workspace;
   float* dz = part + (size_t)G * 9 * C;
   float* kk = dz + (size_t)n * C;
-  if (dy_dtype == VITMI_BF16) {
-    hipLaunchKernelGGL(bn_bwd_stats_kernel<bf16>, dim3(G), dim3(256), 0, st, g, (const bf16*)dy, lddy, dy_img, dy_off,
-                       z, mean, rstd, part);
-  } else {
-    hipLaunchKernelGGL(bn_bwd_stats_kernel<float>, dim3(G), dim3(256), 0, st, g, (const float*)dy, lddy, dy_img,
-                       dy_off, z, mean, rstd, part);
-  }
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + RED_COLS - 1) / RED_COLS), dim3(1024), 0, st, (const float*)part, G, C, n,
-                     dgamma, dbeta, kk);
+  const bool bf = dy_dtype == VITMI_BF16;
+  launch(bf ? untyped(bn_bwd_stats_kernel<bf16>) : untyped(bn_bwd_stats_kernel<float>), dim3(G), dim3(256), st, no_stat,
+         g, dy, lddy, dy_img, dy_off, z, mean, rstd, part);
+  launch(bn_bwd_finalize_kernel, dim3((C + RED_COLS - 1) / RED_COLS), dim3(1024), st, no_stat, (const float*)part, G, C,
+         n, dgamma, dbeta, kk);
   int Gw = (int)(((int64_t)B * H * (C / 4) + 255) / 256);
   if (Gw > G) Gw = G;
-  if (dy_dtype == VITMI_BF16)
-    hipLaunchKernelGGL(dw_bwd_dz_rows_kernel<bf16>, dim3(Gw), dim3(256), 0, st, g, (const bf16*)dy, lddy, dy_img, dy_off,
-                       z, x, mean, rstd, gamma, (const float*)kk, dz, part);
-  else
-    hipLaunchKernelGGL(dw_bwd_dz_rows_kernel<float>, dim3(Gw), dim3(256), 0, st, g, (const float*)dy, lddy, dy_img,
-                       dy_off, z, x, mean, rstd, gamma, (const float*)kk, dz, part);
-  hipLaunchKernelGGL(dw_wgrad_finalize_kernel, dim3((9 * C + RED_COLS - 1) / RED_COLS), dim3(1024), 0, st, (const float*)part, Gw, C,
-                     dwt);
-  hipLaunchKernelGGL(dw_bwd_dx_rows_kernel, dim3(grid_of((int64_t)B * H * (C / 4))), dim3(256), 0, st, g, (const float*)dz,
-                     wt, dx);
+  launch(bf ? untyped(dw_bwd_dz_rows_kernel<bf16>) : untyped(dw_bwd_dz_rows_kernel<float>), dim3(Gw), dim3(256), st,
+         no_stat, g, dy, lddy, dy_img, dy_off, z, x, mean, rstd, gamma, kk, dz, part);
+  launch(dw_wgrad_finalize_kernel, dim3((9 * C + RED_COLS - 1) / RED_COLS), dim3(1024), st, no_stat, (const float*)part,
+         Gw, C, dwt);
+  launch(dw_bwd_dx_rows_kernel, dim3(grid_cap((int64_t)B * H * (C / 4), 256, CVT_BLOCKS)), dim3(256), st, no_stat, g,
+         (const float*)dz, wt, dx);
   VITMI_LAUNCH_CHECK("dwconv_bn_bwd");
   return VITMI_OK;
 }
@@ -715,14 +690,10 @@ extern "C" int vitmi_avgpool3_fwd(int B, int H, int W, int C, const float* x, in
   VITMI_CHECK_ARG(ldy % 4 == 0 && ldy >= C && y_img >= (int64_t)H * W + y_off && y_off >= 0,
                   "avgpool3_fwd: bad output layout");
   VITMI_CHECK_ARG(y_dtype == VITMI_BF16 || y_dtype == VITMI_F32, "avgpool3_fwd: bad dtype");
-  hipStream_t st = (hipStream_t)stream;
   const int64_t work = (int64_t)B * H * W * (C / 4);
-  if (y_dtype == VITMI_BF16)
-    hipLaunchKernelGGL(avgpool3_fwd_kernel<bf16>, dim3(grid_of(work)), dim3(256), 0, st, g, x, (bf16*)y, ldy, y_img,
-                       y_off, count_pad);
-  else
-    hipLaunchKernelGGL(avgpool3_fwd_kernel<float>, dim3(grid_of(work)), dim3(256), 0, st, g, x, (float*)y, ldy, y_img,
-                       y_off, count_pad);
+  launch(y_dtype == VITMI_BF16 ? untyped(avgpool3_fwd_kernel<bf16>) : untyped(avgpool3_fwd_kernel<float>),
+         dim3(grid_cap(work, 256, CVT_BLOCKS)), dim3(256), (hipStream_t)stream, no_stat, g, x, y, ldy, y_img, y_off,
+         count_pad);
   VITMI_LAUNCH_CHECK("avgpool3_fwd");
   return VITMI_OK;
 }
@@ -736,14 +707,10 @@ extern "C" int vitmi_avgpool3_bwd(int B, int H, int W, int C, const void* dy, in
   VITMI_CHECK_ARG(lddy % 4 == 0 && lddy >= C && dy_img >= (int64_t)H * W + dy_off && dy_off >= 0,
                   "avgpool3_bwd: bad dy layout");
   VITMI_CHECK_ARG(dy_dtype == VITMI_BF16 || dy_dtype == VITMI_F32, "avgpool3_bwd: bad dtype");
-  hipStream_t st = (hipStream_t)stream;
   const int64_t work = (int64_t)B * H * W * (C / 4);
-  if (dy_dtype == VITMI_BF16)
-    hipLaunchKernelGGL(avgpool3_bwd_kernel<bf16>, dim3(grid_of(work)), dim3(256), 0, st, g, (const bf16*)dy, lddy,
-                       dy_img, dy_off, dx, count_pad);
-  else
-    hipLaunchKernelGGL(avgpool3_bwd_kernel<float>, dim3(grid_of(work)), dim3(256), 0, st, g, (const float*)dy, lddy,
-                       dy_img, dy_off, dx, count_pad);
+  launch(dy_dtype == VITMI_BF16 ? untyped(avgpool3_bwd_kernel<bf16>) : untyped(avgpool3_bwd_kernel<float>),
+         dim3(grid_cap(work, 256, CVT_BLOCKS)), dim3(256), (hipStream_t)stream, no_stat, g, dy, lddy, dy_img, dy_off,
+         dx, count_pad);
   VITMI_LAUNCH_CHECK("avgpool3_bwd");
   return VITMI_OK;
 }

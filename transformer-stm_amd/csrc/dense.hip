@@ -58,8 +58,6 @@ __global__ void dense_bwd_dw_kernel(int M, int N, int K, const float* __restrict
   if (db && k == 0) db[n] += accb;
 }
 
-static unsigned blocks_for(int64_t work) { return (unsigned)((work + 255) / 256); }
-
 }  // namespace vitmi
 
 using namespace vitmi;
@@ -69,8 +67,8 @@ extern "C" int vitmi_dense_f32_fwd(int M, int N, int K, const float* x, int64_t 
   VITMI_CHECK_ARG(M > 0 && N > 0 && K > 0 && (int64_t)M * N < (1LL << 31), "dense_f32_fwd: bad sizes");
   VITMI_CHECK_ARG(x && w && y && ldx >= K && ldy >= N, "dense_f32_fwd: bad operands");
   VITMI_CHECK_ARG(act == 0 || act == 1, "dense_f32_fwd: act must be 0 (linear) or 1 (relu)");
-  hipLaunchKernelGGL(dense_fwd_kernel, dim3(blocks_for((int64_t)M * N)), dim3(256), 0, (hipStream_t)stream, M, N, K, x,
-                     ldx, w, b, y, ldy, act);
+  launch(dense_fwd_kernel, dim3(grid_cap((int64_t)M * N, 256, GRID_NO_CAP)), dim3(256), (hipStream_t)stream, no_stat, M,
+         N, K, x, ldx, w, b, y, ldy, act);
   VITMI_LAUNCH_CHECK("dense_f32_fwd");
   return VITMI_OK;
 }
@@ -85,11 +83,11 @@ extern "C" int vitmi_dense_f32_bwd(int M, int N, int K, const float* dy, int64_t
   hipStream_t st = (hipStream_t)stream;
   if (dx) {
     VITMI_CHECK_ARG(lddx >= K, "dense_f32_bwd: bad dx stride");
-    hipLaunchKernelGGL(dense_bwd_dx_kernel, dim3(blocks_for((int64_t)M * K)), dim3(256), 0, st, M, N, K, dy, lddy, y,
-                       ldy, w, dx, lddx, act);
+    launch(dense_bwd_dx_kernel, dim3(grid_cap((int64_t)M * K, 256, GRID_NO_CAP)), dim3(256), st, no_stat, M, N, K, dy,
+           lddy, y, ldy, w, dx, lddx, act);
   }
-  hipLaunchKernelGGL(dense_bwd_dw_kernel, dim3(blocks_for((int64_t)N * K)), dim3(256), 0, st, M, N, K, dy, lddy, y,
-                     ldy, x, ldx, dw, db, act);
+  launch(dense_bwd_dw_kernel, dim3(grid_cap((int64_t)N * K, 256, GRID_NO_CAP)), dim3(256), st, no_stat, M, N, K, dy,
+         lddy, y, ldy, x, ldx, dw, db, act);
   VITMI_LAUNCH_CHECK("dense_f32_bwd");
   return VITMI_OK;
 }

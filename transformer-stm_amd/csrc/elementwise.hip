@@ -224,9 +224,8 @@ int launch_folds(const FoldBatch& b, int n, hipStream_t s) {
     bx = x > bx ? x : bx;
     by += 4.0 * (b.j[i].rows + 2) * b.j[i].cols;
   }
-  hipLaunchKernelGGL(fold_kernel, dim3((unsigned)bx, (unsigned)n), dim3(1024), 0, s, b);
+  launch(fold_kernel, dim3((unsigned)bx, (unsigned)n), dim3(1024), s, 0, by, b);
   VITMI_LAUNCH_CHECK("fold");
-  VITMI_STAT(fold_kernel, 0, by);
   return VITMI_OK;
 }
 
@@ -463,12 +462,6 @@ __global__ void droppath_apply_kernel(int64_t M, int64_t N, const float* __restr
   }
 }
 
-static unsigned grid_for(int64_t work, int per_block = 256) {
-  int64_t g = (work + per_block - 1) / per_block;
-  if (g > 8192) g = 8192;
-  return (unsigned)(g < 1 ? 1 : g);
-}
-
 }  // namespace vitmi
 
 using namespace vitmi;
@@ -483,10 +476,8 @@ extern "C" int vitmi_patch_im2col(int dtype, int B, int C, int S, int P, const f
   if (rows == 0) return VITMI_OK;
   hipStream_t s = (hipStream_t)stream;
   const dim3 block((unsigned)((K / 4 + 63) / 64 * 64));
-  if (dtype == VITMI_BF16)
-    hipLaunchKernelGGL(im2col_kernel<bf16>, dim3((unsigned)rows), block, 0, s, img, (bf16*)patches, B, C, S, P);
-  else
-    hipLaunchKernelGGL(im2col_kernel<float>, dim3((unsigned)rows), block, 0, s, img, (float*)patches, B, C, S, P);
+  launch(dtype == VITMI_BF16 ? untyped(im2col_kernel<bf16>) : untyped(im2col_kernel<float>), dim3((unsigned)rows),
+         block, s, no_stat, img, patches, B, C, S, P);
   VITMI_LAUNCH_CHECK("im2col");
   return VITMI_OK;
 }
@@ -495,8 +486,8 @@ extern "C" int vitmi_tokens_assemble(int B, int np, int D, const float* tok, con
                                      const float* pos, float* x, vitmi_stream_t stream) {
   VITMI_CHECK_ARG(D % 4 == 0 && tok && x, "tokens_assemble: bad arguments");
   const int64_t work = (int64_t)B * (np + 1) * D / 4;
-  hipLaunchKernelGGL(tokens_assemble_kernel, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream,
-                     B, np, D, tok, cls, pos, x);
+  launch(tokens_assemble_kernel, dim3(grid_cap(work)), dim3(256), (hipStream_t)stream, no_stat, B, np, D, tok, cls,
+         pos, x);
   VITMI_LAUNCH_CHECK("tokens_assemble");
   return VITMI_OK;
 }
@@ -508,13 +499,12 @@ extern "C" int vitmi_tokens_assemble_bwd(int B, int np, int D, const float* dx, 
   hipStream_t s = (hipStream_t)stream;
   if (dtok || dtok_lp) {
     const int64_t work = (int64_t)B * np * D / 4;
-    hipLaunchKernelGGL(tokens_split_bwd_kernel, dim3(grid_for(work)), dim3(256), 0, s, B, np, D, dx,
-                       dtok, (bf16*)dtok_lp);
+    launch(tokens_split_bwd_kernel, dim3(grid_cap(work)), dim3(256), s, no_stat, B, np, D, dx, dtok, (bf16*)dtok_lp);
   }
   if (dcls || dpos) {
     const int64_t work = (int64_t)(np + 1) * D;
-    hipLaunchKernelGGL(tokens_pos_bwd_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, B,
-                       np + 1, D, dx, dcls, dpos);
+    launch(tokens_pos_bwd_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), s, no_stat, B, np + 1, D, dx, dcls,
+           dpos);
   }
   VITMI_LAUNCH_CHECK("tokens_assemble_bwd");
   return VITMI_OK;
@@ -529,7 +519,7 @@ extern "C" int vitmi_bias_grad(int dtype, int64_t M, int64_t N, const void* dy, 
   VITMI_CHECK_ARG(dtype == VITMI_F32 || dtype == VITMI_BF16, "bias_grad: dtype must be VITMI_F32 or VITMI_BF16");
   VITMI_CHECK_ARG(M >= 0 && N >= 0 && ldy >= N, "bias_grad: ldy >= N required");
   VITMI_CHECK_ARG(dy && db, "bias_grad: null pointer");
-  VITMI_CHECK_ARG((uintptr_t)dy % (dtype == VITMI_BF16 ? 2 : 4) == 0 && (uintptr_t)db % 4 == 0,
+  VITMI_CHECK_ARG(aligned_to(dy, dtype == VITMI_BF16 ? 2 : 4) && aligned_to(db, 4),
                   "bias_grad: dy and db must be aligned to their element (a 16-byte aligned dy with N %% 8 == 0 and "
                   "ldy %% 8 == 0 takes the vector kernel)");
   VITMI_CHECK_ARG(workspace && ws_bytes >= vitmi_bias_grad_workspace_size(M, N), "bias_grad: workspace too small");
@@ -537,31 +527,18 @@ extern "C" int vitmi_bias_grad(int dtype, int64_t M, int64_t N, const void* dy, 
   hipStream_t s = (hipStream_t)stream;
   const int Z = colsum_splits(M, N);
   const int64_t rows_per = (M + Z - 1) / Z;
-  const bool vec = (N % 8 == 0) && (ldy % 8 == 0) && ((uintptr_t)dy % 16 == 0);
+  const bool vec = (N % 8 == 0) && (ldy % 8 == 0) && aligned_to(dy, 16), bf = dtype == VITMI_BF16;
+  const double bytes = (double)M * N * (bf ? 2 : 4);   // dy read once
   if (vec) {
     dim3 grid((unsigned)((N + 511) / 512), Z);
     int lshift = 6;   // lanes per row: the smallest power of two >= N / 8, at most 64
     while (lshift > 0 && (int64_t)8 << (lshift - 1) >= N) --lshift;
-    if (dtype == VITMI_BF16) {
-      hipLaunchKernelGGL(colsum8_kernel<bf16>, grid, dim3(256), 0, s, M, N, (const bf16*)dy, ldy,
-                         (float*)workspace, rows_per, lshift);
-      VITMI_STAT(colsum8_kernel<bf16>, 0, (double)M * N * 2);
-    } else {
-      hipLaunchKernelGGL(colsum8_kernel<float>, grid, dim3(256), 0, s, M, N, (const float*)dy, ldy,
-                         (float*)workspace, rows_per, lshift);
-      VITMI_STAT(colsum8_kernel<float>, 0, (double)M * N * 4);
-    }
+    launch(bf ? untyped(colsum8_kernel<bf16>) : untyped(colsum8_kernel<float>), grid, dim3(256), s, 0, bytes, M, N, dy,
+           ldy, (float*)workspace, rows_per, lshift);
   } else {
     dim3 grid((unsigned)((N + 255) / 256), Z);
-    if (dtype == VITMI_BF16) {
-      hipLaunchKernelGGL(colsum_kernel<bf16>, grid, dim3(256), 0, s, M, N, (const bf16*)dy, ldy,
-                         (float*)workspace, rows_per);
-      VITMI_STAT(colsum_kernel<bf16>, 0, (double)M * N * 2);
-    } else {
-      hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, s, M, N, (const float*)dy, ldy,
-                         (float*)workspace, rows_per);
-      VITMI_STAT(colsum_kernel<float>, 0, (double)M * N * 4);
-    }
+    launch(bf ? untyped(colsum_kernel<bf16>) : untyped(colsum_kernel<float>), grid, dim3(256), s, 0, bytes, M, N, dy,
+           ldy, (float*)workspace, rows_per);
   }
   VITMI_LAUNCH_CHECK("bias_grad");
   return fold_rows((const float*)workspace, Z, N, N, db, s);
@@ -571,8 +548,8 @@ extern "C" int vitmi_head_fwd(int B, int D, int C, const float* y, int64_t ldy, 
                               const float* b, float* logits, vitmi_stream_t stream) {
   VITMI_CHECK_ARG(y && w && logits && B > 0 && C > 0, "head_fwd: bad arguments");
   const int waves = B * C;
-  hipLaunchKernelGGL(head_fwd_kernel, dim3((waves + 3) / 4), dim3(256), 0, (hipStream_t)stream, B, D, C,
-                     y, ldy, w, b, logits);
+  launch(head_fwd_kernel, dim3((waves + 3) / 4), dim3(256), (hipStream_t)stream, no_stat, B, D, C, y, ldy, w, b,
+         logits);
   VITMI_LAUNCH_CHECK("head_fwd");
   return VITMI_OK;
 }
@@ -583,10 +560,10 @@ extern "C" int vitmi_head_bwd(int B, int D, int C, const float* dlogits, const f
   VITMI_CHECK_ARG(dlogits && y && w && dy && dw, "head_bwd: bad arguments");
   VITMI_CHECK_ARG(C <= 65535, "head_bwd: at most 65535 classes");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(head_bwd_dy_kernel, dim3((unsigned)(((int64_t)B * D + 255) / 256)), dim3(256), 0, s,
-                     B, D, C, dlogits, w, dy);
-  hipLaunchKernelGGL(head_bwd_dw_kernel, dim3((unsigned)((D + 63) / 64), (unsigned)C), dim3(1024), 0, s,
-                     B, D, C, dlogits, y, ldy, dw, db);
+  launch(head_bwd_dy_kernel, dim3((unsigned)(((int64_t)B * D + 255) / 256)), dim3(256), s, no_stat, B, D, C, dlogits,
+         w, dy);
+  launch(head_bwd_dw_kernel, dim3((unsigned)((D + 63) / 64), (unsigned)C), dim3(1024), s, no_stat, B, D, C, dlogits, y,
+         ldy, dw, db);
   VITMI_LAUNCH_CHECK("head_bwd");
   return VITMI_OK;
 }
@@ -595,30 +572,25 @@ extern "C" int vitmi_loss_fwd_bwd(int kind, int B, int C, const float* logits, c
                                   float* loss, float* dlogits, vitmi_stream_t stream) {
   VITMI_CHECK_ARG(kind == VITMI_LOSS_CE || kind == VITMI_LOSS_MSE, "loss: bad kind %d", kind);
   VITMI_CHECK_ARG(logits && target && (loss || dlogits) && B > 0 && C > 0, "loss: bad arguments");
-  hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, kind, B, C, logits, target,
-                     loss, dlogits);
+  launch(loss_kernel, dim3(1), dim3(256), (hipStream_t)stream, no_stat, kind, B, C, logits, target, loss, dlogits);
   VITMI_LAUNCH_CHECK("loss");
   return VITMI_OK;
 }
 
 extern "C" int vitmi_cast_f32_bf16(int64_t n, const float* src, void* dst, vitmi_stream_t stream) {
   VITMI_CHECK_ARG(src && dst, "cast: null pointer");
-  VITMI_CHECK_ARG(((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0, "cast: 16-byte alignment required");
+  VITMI_CHECK_ARG(aligned_to(src, 16) && aligned_to(dst, 16), "cast: 16-byte alignment required");
   if (n == 0) return VITMI_OK;
-  hipLaunchKernelGGL(cast_kernel, dim3(grid_for(n / 8 + 1)), dim3(256), 0, (hipStream_t)stream, n, src,
-                     (bf16*)dst);
-  VITMI_STAT(cast_kernel, 0, 6.0 * n);
+  launch(cast_kernel, dim3(grid_cap(n / 8 + 1)), dim3(256), (hipStream_t)stream, 0, 6.0 * n, n, src, (bf16*)dst);
   VITMI_LAUNCH_CHECK("cast");
   return VITMI_OK;
 }
 
 extern "C" int vitmi_cast_bf16_f32(int64_t n, const void* src, float* dst, vitmi_stream_t stream) {
   VITMI_CHECK_ARG(src && dst, "cast_bf16_f32: null pointer");
-  VITMI_CHECK_ARG(((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0,
-                  "cast_bf16_f32: 16-byte alignment required");
+  VITMI_CHECK_ARG(aligned_to(src, 16) && aligned_to(dst, 16), "cast_bf16_f32: 16-byte alignment required");
   if (n == 0) return VITMI_OK;
-  hipLaunchKernelGGL(cast_up_kernel, dim3(grid_for(n / 8 + 1)), dim3(256), 0, (hipStream_t)stream, n,
-                     (const bf16*)src, dst);
+  launch(cast_up_kernel, dim3(grid_cap(n / 8 + 1)), dim3(256), (hipStream_t)stream, no_stat, n, (const bf16*)src, dst);
   VITMI_LAUNCH_CHECK("cast_bf16_f32");
   return VITMI_OK;
 }
@@ -630,15 +602,11 @@ extern "C" int vitmi_dropout_apply(int64_t M, int64_t N, const float* x, int64_t
   VITMI_CHECK_ARG(y_dtype == VITMI_F32 || y_dtype == VITMI_BF16, "dropout_apply: bad dtype %d", y_dtype);
   VITMI_CHECK_ARG(N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= N && ldy >= N,
                   "dropout_apply: N and leading dims must be multiples of 4");
-  VITMI_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 8) == 0, "dropout_apply: alignment");
+  VITMI_CHECK_ARG(aligned_to(x, 16) && aligned_to(y, 8), "dropout_apply: alignment");
   if (M == 0 || N == 0) return VITMI_OK;
-  const unsigned grid = grid_for(M * N / 4);
-  if (y_dtype == VITMI_F32)
-    hipLaunchKernelGGL(dropout_apply_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, M, N, x, ldx,
-                       (float*)y, ldy, seed, site, thresh, scale);
-  else
-    hipLaunchKernelGGL(dropout_apply_kernel<bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, M, N, x, ldx,
-                       (bf16*)y, ldy, seed, site, thresh, scale);
+  launch(y_dtype == VITMI_F32 ? untyped(dropout_apply_kernel<float>) : untyped(dropout_apply_kernel<bf16>),
+         dim3(grid_cap(M * N / 4)), dim3(256), (hipStream_t)stream, no_stat, M, N, x, ldx, y, ldy, seed, site, thresh,
+         scale);
   VITMI_LAUNCH_CHECK("dropout_apply");
   return VITMI_OK;
 }
@@ -652,7 +620,7 @@ extern "C" int vitmi_droppath_apply(int64_t M, int64_t N, const float* x, int64_
   VITMI_CHECK_ARG(M >= 0 && N >= 0, "droppath_apply: negative size");
   VITMI_CHECK_ARG(N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= N && ldy >= N,
                   "droppath_apply: N and leading dims must be multiples of 4");
-  VITMI_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 8) == 0, "droppath_apply: alignment");
+  VITMI_CHECK_ARG(aligned_to(x, 16) && aligned_to(y, 8), "droppath_apply: alignment");
   VITMI_CHECK_ARG(rows_per_sample >= 1, "droppath_apply: rows_per_sample must be >= 1 (got %lld)",
                   (long long)rows_per_sample);
   VITMI_CHECK_ARG(M % rows_per_sample == 0, "droppath_apply: M = %lld is not a multiple of rows_per_sample = %lld",
@@ -660,25 +628,16 @@ extern "C" int vitmi_droppath_apply(int64_t M, int64_t N, const float* x, int64_
   VITMI_CHECK_ARG(path_map_exact(M, rows_per_sample), "droppath_apply: M * rows_per_sample must be <= 2^32 "
                   "(the row -> sample mapping is exact only there)");
   if (M == 0 || N == 0) return VITMI_OK;
-  const unsigned grid = grid_for(M * N / 4);
   const uint32_t S = (uint32_t)rows_per_sample, magic = path_magic(S);
-  const hipStream_t s = (hipStream_t)stream;
   // drop_thresh 0 keeps every element: the sample factor alone
-#define VITMI_DP_LAUNCH(TO, DROP)                                                                            \
-  do {                                                                                                       \
-    hipLaunchKernelGGL((droppath_apply_kernel<TO, DROP>), dim3(grid), dim3(256), 0, s, M, N, x, ldx, (TO*)y, \
-                       ldy, S, magic, seed, path_site, path_thresh, path_scale, drop_site, drop_thresh,      \
-                       drop_scale);                                                                          \
-    VITMI_STAT((droppath_apply_kernel<TO, DROP>), 0, (double)M * N * (4 + sizeof(TO)));                      \
-  } while (0)
-  if (y_dtype == VITMI_F32) {
-    if (drop_thresh) VITMI_DP_LAUNCH(float, true);
-    else VITMI_DP_LAUNCH(float, false);
-  } else {
-    if (drop_thresh) VITMI_DP_LAUNCH(bf16, true);
-    else VITMI_DP_LAUNCH(bf16, false);
-  }
-#undef VITMI_DP_LAUNCH
+  const bool f32 = y_dtype == VITMI_F32, drop = drop_thresh != 0;
+  const auto kern = f32 ? (drop ? untyped(droppath_apply_kernel<float, true>)
+                                : untyped(droppath_apply_kernel<float, false>))
+                        : (drop ? untyped(droppath_apply_kernel<bf16, true>)
+                                : untyped(droppath_apply_kernel<bf16, false>));
+  // x read, y written
+  launch(kern, dim3(grid_cap(M * N / 4)), dim3(256), (hipStream_t)stream, 0, (double)M * N * (4 + (f32 ? 4 : 2)), M, N,
+         x, ldx, y, ldy, S, magic, seed, path_site, path_thresh, path_scale, drop_site, drop_thresh, drop_scale);
   VITMI_LAUNCH_CHECK("droppath_apply");
   return VITMI_OK;
 }

@@ -1615,7 +1615,6 @@ __global__ __launch_bounds__(256) void tail_colsum_kernel(GemmArgs g) {
 // GEMM kernel policy: 0 = auto, 1 = always the 128x128 kernel, 2 = always gemm256 (bf16),
 // 3 = gemm256 on an 8-block persistent grid (every block walks many tiles; tests only)
 static int g_policy = 0;
-static int g_cus = 256;   // compute units of the current device (set on first use)
 
 // CUs the persistent grid leaves free (vitmi_gemm_set_reserved_cus).  Atomic: the DP reducer may
 // change it from a thread other than the one launching GEMMs.
@@ -1623,16 +1622,6 @@ static std::atomic<int> g_reserved{0};
 #ifdef VITMI_GEMM_STAMPS
 static unsigned long long* g_stamps = nullptr;
 #endif
-
-static void init_cus() {
-  static bool done = false;
-  if (done) return;
-  int dev = 0;
-  hipDeviceProp_t p;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0)
-    g_cus = p.multiProcessorCount;
-  done = true;
-}
 
 static int64_t splits_for(int64_t tiles, int64_t ktiles, int64_t target, int64_t cap = 64) {
   int64_t want = target / tiles;
@@ -1650,13 +1639,12 @@ static bool use256(int dtype, int64_t M, int64_t N, int64_t K = 0, bool split = 
   if (g_policy >= 2) return true;
   const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256);
   if (tiles >= 16) return true;
-  init_cus();
   return split && tiles * splits_for(tiles, (K + 63) / 64, 256) >= 128;
 }
 
 // persistent grid of the gemm256 launch for nwg tiles and `splits` K-slabs
 static int grid256(int nwg, int splits) {
-  int gx = (g_cus - g_reserved.load(std::memory_order_relaxed)) / splits;
+  int gx = (device_cus() - g_reserved.load(std::memory_order_relaxed)) / splits;
   if (gx < 8 || g_policy == 3) gx = 8;   // policy 3: force many tiles per block (tests)
   return gx > nwg ? nwg : gx;
 }
@@ -1679,7 +1667,6 @@ static bool tail_plan(int nwg, int gx, int nk, int& S, int& ks, int& ntail) {
 }
 
 static size_t tail_ws_bytes(int64_t M, int64_t N, int64_t K) {
-  init_cus();
   const int nwg = (int)(((M + 255) / 256) * ((N + 255) / 256));
   int S, ks, ntail;
   if (nwg <= 0 || !tail_plan(nwg, grid256(nwg, 1), (int)((K + 63) / 64), S, ks, ntail)) return 0;
@@ -1829,8 +1816,7 @@ static int choose_splits(int dtype, int64_t M, int64_t N, int64_t K, int reserve
   const int64_t ktiles = (K + bk_of(dtype) - 1) / bk_of(dtype);
   // about one round of the CUs the persistent grid may use: with reserved CUs (DP overlap) a
   // fixed 256 left a few units for a second full round (fc1 wgrad 262 -> 440 us at 8 reserved)
-  init_cus();
-  const int avail = g_cus - reserved > 8 ? g_cus - reserved : 8;
+  const int avail = device_cus() - reserved > 8 ? device_cus() - reserved : 8;
   // small outputs (the CvT's 64x64 .. 256x256 weight gradients over 16-262 k tokens) may take up
   // to 512 slabs while all of them stay under 32 MiB: with the usual cap of 64 a one-tile output
   // ran 64 workgroups on 256 CUs
@@ -1926,7 +1912,6 @@ static int gemm_impl(GemmReq q) {
 
   const bool big = f8 || use256(dtype, M, N, K, q.allow_split && epi == VITMI_EPI_ACCUM);
   if (big) {
-    init_cus();
     VITMI_CHECK_ARG(g.ldc % 8 == 0 && (g.ldr % 4) == 0 && (g.ldaux % 8) == 0 && ((uintptr_t)g.C % 16) == 0,
                     "gemm: 16-byte aligned C/aux/residual rows required");
     VITMI_CHECK_ARG(g.bias == nullptr || ((uintptr_t)g.bias % 16) == 0, "gemm: bias must be 16-byte aligned");
@@ -1981,19 +1966,14 @@ static int gemm_impl(GemmReq q) {
   if (int rc = run(EpiPartial::code, VITMI_F32, gp, splits)) return rc;
   const int64_t n = M * N;
   if ((n + 3) / 4 <= SMALL_RED_MAX && splits >= 16) {
-    hipLaunchKernelGGL(splitk_reduce_small_kernel, dim3((unsigned)(((n + 3) / 4 + 63) / 64)), dim3(1024), 0, q.s,
-                       (const float*)q.ws, (float*)g.C, n, splits, M * N);
+    launch(splitk_reduce_small_kernel, dim3((unsigned)(((n + 3) / 4 + 63) / 64)), dim3(1024), q.s, 0,
+           (double)n * 4 * (splits + 2), (const float*)q.ws, (float*)g.C, n, splits, M * N);
     VITMI_LAUNCH_CHECK("splitk_reduce_small_kernel");
-    VITMI_STAT(splitk_reduce_small_kernel, 0, (double)n * 4 * (splits + 2));
     return VITMI_OK;
   }
-  int blocks = (int)((n / 4 + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, q.s, (const float*)q.ws,
-                     (float*)g.C, n, splits, M * N);
+  launch(splitk_reduce_kernel, dim3(grid_cap(n / 4, 256, 4096)), dim3(256), q.s, 0, (double)n * 4 * (splits + 2),
+         (const float*)q.ws, (float*)g.C, n, splits, M * N);
   VITMI_LAUNCH_CHECK("splitk_reduce_kernel");
-  VITMI_STAT(splitk_reduce_kernel, 0, (double)n * 4 * (splits + 2));
   return VITMI_OK;
 }
 
@@ -2041,14 +2021,13 @@ static bool group_ok(int dtype, int n, int64_t M, const WgProb* pr) {
 }
 
 static void group_plan(int n, int64_t M, const WgProb* pr, int64_t& tiles, int& S, size_t& need) {
-  init_cus();
   tiles = 0;
   int64_t mn = 0;
   for (int q = 0; q < n; ++q) {
     tiles += ((pr[q].N + 255) / 256) * ((pr[q].K + 255) / 256);
     mn += pr[q].N * pr[q].K;
   }
-  S = group_splits(tiles, (M + 63) / 64, g_cus);
+  S = group_splits(tiles, (M + 63) / 64, device_cus());
   need = (size_t)S * mn * sizeof(float);
 }
 
@@ -2153,8 +2132,7 @@ extern "C" int vitmi_gemm_set_stamps(void* buf) {
 #endif
 
 extern "C" int vitmi_gemm_set_reserved_cus(int n) {
-  init_cus();
-  return g_reserved.exchange(n < 0 ? 0 : (n > g_cus - 8 ? g_cus - 8 : n));
+  return g_reserved.exchange(n < 0 ? 0 : (n > device_cus() - 8 ? device_cus() - 8 : n));
 }
 
 extern "C" int vitmi_gemm_set_policy(int policy) {

@@ -307,67 +307,54 @@ __global__ __launch_bounds__(256) void ln_bwd_small_kernel(
   }
 }
 
-// a null pointer (an output that is not asked for) counts as aligned
-static bool aligned_to(const void* p, uintptr_t bytes) { return (uintptr_t)p % bytes == 0; }
-
 static constexpr int LN_BWD_BLOCKS = 512;
 static int ln_blocks_bwd(int64_t M) {
   int64_t g = (M + 3) / 4;
   return (int)(g < LN_BWD_BLOCKS ? (g < 1 ? 1 : g) : LN_BWD_BLOCKS);
 }
 
+// The kernel instance of a call, picked from the runtime dtypes (common.h untyped); the entry points
+// launch it once.  NV = ceil(D / 256) float4 per lane, compiled for 1, 2, 3, 4 and 8 (D <= 2048).
+using ln_fwd_t = decltype(untyped(ln_fwd_kernel<1, float>));
 template <int NV>
-static void ln_fwd_launch(hipStream_t s, int64_t M, int D, const float* x, int64_t ldx,
-                          const float* gamma, const float* beta, float eps, void* y, int ydt,
-                          int64_t ldy, float* mean, float* rstd) {
-  dim3 grid((unsigned)((M + 3) / 4));
-  if (ydt == VITMI_BF16X3) {
-    hipLaunchKernelGGL((ln_fwd_kernel<NV, SplitX3>), grid, dim3(256), 0, s, M, D, x, ldx, gamma, beta, eps,
-                       (SplitX3*)y, ldy, mean, rstd);
-    VITMI_STAT((ln_fwd_kernel<NV, SplitX3>), 0, (double)M * D * (4 + 6) + 8.0 * M);
-    return;
+static ln_fwd_t ln_fwd_pick(int ydt) {
+  switch (ydt) {
+    case VITMI_BF16X3: return untyped(ln_fwd_kernel<NV, SplitX3>);
+    case VITMI_BF16F8: return untyped(ln_fwd_kernel<NV, SplitF8>);
+    case VITMI_BF16F8W: return untyped(ln_fwd_kernel<NV, SplitF8W>);
+    case VITMI_BF16: return untyped(ln_fwd_kernel<NV, bf16>);
+    default: return untyped(ln_fwd_kernel<NV, float>);
   }
-  if (ydt == VITMI_BF16F8) {
-    hipLaunchKernelGGL((ln_fwd_kernel<NV, SplitF8>), grid, dim3(256), 0, s, M, D, x, ldx, gamma, beta, eps,
-                       (SplitF8*)y, ldy, mean, rstd);
-    VITMI_STAT((ln_fwd_kernel<NV, SplitF8>), 0, (double)M * D * (4 + 4) + 8.0 * M);
-    return;
+}
+static ln_fwd_t ln_fwd_pick(int D, int ydt) {
+  switch ((D + 255) / 256) {
+    case 1: return ln_fwd_pick<1>(ydt);
+    case 2: return ln_fwd_pick<2>(ydt);
+    case 3: return ln_fwd_pick<3>(ydt);
+    case 4: return ln_fwd_pick<4>(ydt);
+    default: return ln_fwd_pick<8>(ydt);
   }
-  if (ydt == VITMI_BF16F8W) {
-    hipLaunchKernelGGL((ln_fwd_kernel<NV, SplitF8W>), grid, dim3(256), 0, s, M, D, x, ldx, gamma, beta, eps,
-                       (SplitF8W*)y, ldy, mean, rstd);
-    VITMI_STAT((ln_fwd_kernel<NV, SplitF8W>), 0, (double)M * D * (4 + 3) + 8.0 * M);
-    return;
-  }
-  if (ydt == VITMI_BF16)
-    hipLaunchKernelGGL((ln_fwd_kernel<NV, bf16>), grid, dim3(256), 0, s, M, D, x, ldx, gamma, beta,
-                       eps, (bf16*)y, ldy, mean, rstd);
-  else
-    hipLaunchKernelGGL((ln_fwd_kernel<NV, float>), grid, dim3(256), 0, s, M, D, x, ldx, gamma, beta,
-                       eps, (float*)y, ldy, mean, rstd);
-  // x (fp32) read, y written, mean/rstd written
-  const double ysz = ydt == VITMI_BF16 ? 2 : 4;
-  if (ydt == VITMI_BF16) VITMI_STAT((ln_fwd_kernel<NV, bf16>), 0, (double)M * D * (4 + ysz) + 8.0 * M);
-  else VITMI_STAT((ln_fwd_kernel<NV, float>), 0, (double)M * D * (4 + ysz) + 8.0 * M);
 }
 
-template <int NV, typename TDY>
-static void ln_bwd_launch(hipStream_t s, int G, int64_t M, int D, const void* dy, int64_t lddy,
-                          const float* x, int64_t ldx, const float* mean, const float* rstd,
-                          const float* gamma, const float* dres, int64_t ldres, float* dx,
-                          int64_t lddx, void* dx_lp, int64_t lddx_lp, float* part) {
-  if (dx_lp)
-    hipLaunchKernelGGL((ln_bwd_kernel<NV, TDY, true>), dim3(G), dim3(256), 0, s, M, D,
-                       (const TDY*)dy, lddy, x, ldx, mean, rstd, gamma, dres, ldres, dx, lddx,
-                       (bf16*)dx_lp, lddx_lp, part);
-  else
-    hipLaunchKernelGGL((ln_bwd_kernel<NV, TDY, false>), dim3(G), dim3(256), 0, s, M, D,
-                       (const TDY*)dy, lddy, x, ldx, mean, rstd, gamma, dres, ldres, dx, lddx,
-                       (bf16*)nullptr, 0, part);
-  // dy + x (+ dres) read, dx (+ bf16 copy) written
-  const double b = (double)M * D * (sizeof(TDY) + 4 + (dres ? 4 : 0) + 4 + (dx_lp ? 2 : 0)) + 8.0 * M;
-  if (dx_lp) VITMI_STAT((ln_bwd_kernel<NV, TDY, true>), 0, b);
-  else VITMI_STAT((ln_bwd_kernel<NV, TDY, false>), 0, b);
+using ln_bwd_t = decltype(untyped(ln_bwd_kernel<1, float, false>));
+template <int NV>
+static ln_bwd_t ln_bwd_pick(bool bf, bool lp) {
+  if (bf) return lp ? untyped(ln_bwd_kernel<NV, bf16, true>) : untyped(ln_bwd_kernel<NV, bf16, false>);
+  return lp ? untyped(ln_bwd_kernel<NV, float, true>) : untyped(ln_bwd_kernel<NV, float, false>);
+}
+static ln_bwd_t ln_bwd_pick(int D, bool bf, bool lp) {
+  switch ((D + 255) / 256) {
+    case 1: return ln_bwd_pick<1>(bf, lp);
+    case 2: return ln_bwd_pick<2>(bf, lp);
+    case 3: return ln_bwd_pick<3>(bf, lp);
+    case 4: return ln_bwd_pick<4>(bf, lp);
+    default: return ln_bwd_pick<8>(bf, lp);
+  }
+}
+template <int L>
+static auto ln_bwd_small_pick(bool bf, bool lp) {
+  if (bf) return lp ? untyped(ln_bwd_small_kernel<L, bf16, true>) : untyped(ln_bwd_small_kernel<L, bf16, false>);
+  return lp ? untyped(ln_bwd_small_kernel<L, float, true>) : untyped(ln_bwd_small_kernel<L, float, false>);
 }
 
 }  // namespace vitmi
@@ -395,35 +382,21 @@ extern "C" int vitmi_layernorm_fwd(int64_t M, int D, const float* x, int64_t ldx
                       aligned_to(y, y_dtype == VITMI_F32 ? 16 : 8),
                   "layernorm_fwd: x, gamma, beta and an fp32 y must be 16-byte aligned, a bf16 y 8-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  if ((D == 64 || D == 128) && y_dtype != VITMI_BF16X3 && y_dtype != VITMI_BF16F8 &&
-      y_dtype != VITMI_BF16F8W) {
+  // x (fp32) read, y written (6, 4 and 3 bytes per element of the [hi | hi | lo], [hi | hi8 | lo8] and
+  // [hi | hi8] rows), mean/rstd written
+  const int ysz = y_dtype == VITMI_BF16X3 ? 6 : y_dtype == VITMI_BF16F8W ? 3 : y_dtype == VITMI_BF16 ? 2 : 4;
+  const double bytes = (double)M * D * (4 + ysz) + 8.0 * M;
+  const bool bf = y_dtype == VITMI_BF16;
+  if ((D == 64 || D == 128) && (bf || y_dtype == VITMI_F32)) {
     const int rw = 64 / (D / 4);
     const dim3 grid((unsigned)((M + 4 * rw - 1) / (4 * rw)));
-    // x (fp32) read, y written, mean/rstd written: the byte formula of ln_fwd_launch
-#define LNF(LL, TY)                                                                                          \
-  do {                                                                                                       \
-    hipLaunchKernelGGL((ln_fwd_small_kernel<LL, TY>), grid, dim3(256), 0, s, M, x, ldx, gamma, beta, eps,    \
-                       (TY*)y, ldy, mean, rstd);                                                             \
-    VITMI_STAT((ln_fwd_small_kernel<LL, TY>), 0, (double)M * D * (4 + sizeof(TY)) + 8.0 * M);                \
-  } while (0)
-    if (D == 64) {
-      if (y_dtype == VITMI_BF16) LNF(16, bf16);
-      else LNF(16, float);
-    } else {
-      if (y_dtype == VITMI_BF16) LNF(32, bf16);
-      else LNF(32, float);
-    }
-#undef LNF
-    VITMI_LAUNCH_CHECK("layernorm_fwd");
-    return VITMI_OK;
-  }
-  const int nv = (D + 255) / 256;
-  switch (nv) {
-    case 1: ln_fwd_launch<1>(s, M, D, x, ldx, gamma, beta, eps, y, y_dtype, ldy, mean, rstd); break;
-    case 2: ln_fwd_launch<2>(s, M, D, x, ldx, gamma, beta, eps, y, y_dtype, ldy, mean, rstd); break;
-    case 3: ln_fwd_launch<3>(s, M, D, x, ldx, gamma, beta, eps, y, y_dtype, ldy, mean, rstd); break;
-    case 4: ln_fwd_launch<4>(s, M, D, x, ldx, gamma, beta, eps, y, y_dtype, ldy, mean, rstd); break;
-    default: ln_fwd_launch<8>(s, M, D, x, ldx, gamma, beta, eps, y, y_dtype, ldy, mean, rstd); break;
+    const auto small = D == 64
+                           ? (bf ? untyped(ln_fwd_small_kernel<16, bf16>) : untyped(ln_fwd_small_kernel<16, float>))
+                           : (bf ? untyped(ln_fwd_small_kernel<32, bf16>) : untyped(ln_fwd_small_kernel<32, float>));
+    launch(small, grid, dim3(256), s, 0, bytes, M, x, ldx, gamma, beta, eps, y, ldy, mean, rstd);
+  } else {
+    launch(ln_fwd_pick(D, y_dtype), dim3((unsigned)((M + 3) / 4)), dim3(256), s, 0, bytes, M, D, x, ldx, gamma, beta,
+           eps, y, ldy, mean, rstd);
   }
   VITMI_LAUNCH_CHECK("layernorm_fwd");
   return VITMI_OK;
@@ -457,45 +430,15 @@ extern "C" int vitmi_layernorm_bwd(int64_t M, int D, const void* dy, int dy_dtyp
   hipStream_t s = (hipStream_t)stream;
   const int G = ln_blocks_bwd(M);
   float* part = (float*)workspace;
-  const int nv = (D + 255) / 256;
-  if (D == 64 || D == 128) {
-    // dy + x (+ dres) read, dx (+ bf16 copy) written: the byte formula of ln_bwd_launch
-#define LNS(LL, TD, LPB)                                                                                              \
-  do {                                                                                                                \
-    hipLaunchKernelGGL((ln_bwd_small_kernel<LL, TD, LPB>), dim3(G), dim3(256), 0, s, M, (const TD*)dy, lddy, x, ldx,  \
-                       mean, rstd, gamma, dres, ldres, dx, lddx, (bf16*)dx_lp, lddx_lp, part);                        \
-    VITMI_STAT((ln_bwd_small_kernel<LL, TD, LPB>), 0,                                                                 \
-               (double)M * D * (sizeof(TD) + 4 + (dres ? 4 : 0) + 4 + (LPB ? 2 : 0)) + 8.0 * M);                      \
-  } while (0)
-    const bool bf = dy_dtype == VITMI_BF16, lp = dx_lp != nullptr;
-    if (D == 64) {
-      if (bf) { if (lp) LNS(16, bf16, true); else LNS(16, bf16, false); }
-      else { if (lp) LNS(16, float, true); else LNS(16, float, false); }
-    } else {
-      if (bf) { if (lp) LNS(32, bf16, true); else LNS(32, bf16, false); }
-      else { if (lp) LNS(32, float, true); else LNS(32, float, false); }
-    }
-#undef LNS
-    VITMI_LAUNCH_CHECK("layernorm_bwd");
-    if (int rc = fold_rows(part, G, D, D, dgamma, s)) return rc;
-    if (int rc = fold_rows(part + (int64_t)G * D, G, D, D, dbeta, s)) return rc;
-    return fold_rows(part + 2LL * G * D, G, D, D, dxsum, s);
-  }
-#define LNB(NV)                                                                                  \
-  if (dy_dtype == VITMI_BF16)                                                                    \
-    ln_bwd_launch<NV, bf16>(s, G, M, D, dy, lddy, x, ldx, mean, rstd, gamma, dres, ldres, dx,    \
-                            lddx, dx_lp, lddx_lp, part);                                         \
-  else                                                                                           \
-    ln_bwd_launch<NV, float>(s, G, M, D, dy, lddy, x, ldx, mean, rstd, gamma, dres, ldres, dx,   \
-                             lddx, dx_lp, lddx_lp, part);
-  switch (nv) {
-    case 1: LNB(1) break;
-    case 2: LNB(2) break;
-    case 3: LNB(3) break;
-    case 4: LNB(4) break;
-    default: LNB(8) break;
-  }
-#undef LNB
+  // dy + x (+ dres) read, dx (+ bf16 copy) written
+  const bool bf = dy_dtype == VITMI_BF16, lp = dx_lp != nullptr;
+  const double bytes = (double)M * D * ((bf ? 2 : 4) + 4 + (dres ? 4 : 0) + 4 + (lp ? 2 : 0)) + 8.0 * M;
+  if (D == 64 || D == 128)
+    launch(D == 64 ? ln_bwd_small_pick<16>(bf, lp) : ln_bwd_small_pick<32>(bf, lp), dim3(G), dim3(256), s, 0, bytes, M,
+           dy, lddy, x, ldx, mean, rstd, gamma, dres, ldres, dx, lddx, dx_lp, lddx_lp, part);
+  else
+    launch(ln_bwd_pick(D, bf, lp), dim3(G), dim3(256), s, 0, bytes, M, D, dy, lddy, x, ldx, mean, rstd, gamma, dres,
+           ldres, dx, lddx, dx_lp, lp ? lddx_lp : (int64_t)0, part);
   VITMI_LAUNCH_CHECK("layernorm_bwd");
   // the per-block partials of dgamma (rows 0..G-1), dbeta (G..2G-1), colsum(dx) (2G..3G-1)
   if (int rc = fold_rows(part, G, D, D, dgamma, s)) return rc;

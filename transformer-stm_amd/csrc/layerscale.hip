@@ -143,8 +143,6 @@ static int dgamma_splits(int64_t M, int64_t N) {
   return (int)(z < 1 ? 1 : z);
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
 }  // namespace vitmi
 
 using namespace vitmi;
@@ -160,21 +158,13 @@ extern "C" int vitmi_layerscale_fold(int64_t N, int64_t K, const float* w, const
                   (long long)K);
   VITMI_CHECK_ARG(N <= (int64_t)0x7fffffff && K <= (int64_t)0x7fffffff && N * (K / 8) <= (int64_t)0x7fffffff,
                   "layerscale_fold: N * K / 8 must be < 2^31");
-  VITMI_CHECK_ARG(aligned16(w) && aligned16(w_eff), "layerscale_fold: w and w_eff must be 16-byte aligned");
+  VITMI_CHECK_ARG(aligned_to(w, 16) && aligned_to(w_eff, 16), "layerscale_fold: w and w_eff must be 16-byte aligned");
   const uint32_t k8 = (uint32_t)(K / 8), units = (uint32_t)(N * (K / 8));
+  const bool f32 = w_dtype == VITMI_F32;
   // 8 blocks per CU at the most: a [768, 3072] weight is 1152 blocks, every unit touched once
-  int64_t blocks = ((int64_t)units + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  const hipStream_t s = (hipStream_t)stream;
-  if (w_dtype == VITMI_F32) {
-    hipLaunchKernelGGL(layerscale_fold_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, units, k8, N, w, gamma,
-                       (float*)w_eff, bias, bias_eff);
-    VITMI_STAT(layerscale_fold_kernel<float>, 0, 8.0 * N * K);
-  } else {
-    hipLaunchKernelGGL(layerscale_fold_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, s, units, k8, N, w, gamma,
-                       (bf16*)w_eff, bias, bias_eff);
-    VITMI_STAT(layerscale_fold_kernel<bf16>, 0, 6.0 * N * K);
-  }
+  launch(f32 ? untyped(layerscale_fold_kernel<float>) : untyped(layerscale_fold_kernel<bf16>),
+         dim3(grid_cap(units, 256, 2048)), dim3(256), (hipStream_t)stream, 0, (f32 ? 8.0 : 6.0) * N * K, units, k8, N,
+         w, gamma, w_eff, bias, bias_eff);
   VITMI_LAUNCH_CHECK("layerscale_fold");
   return VITMI_OK;
 }
@@ -191,28 +181,20 @@ extern "C" int vitmi_layerscale_bwd(int64_t N, int64_t K, const float* w, const 
   VITMI_CHECK_ARG(K >= 8 && K % 8 == 0, "layerscale_bwd: K must be a positive multiple of 8 (got %lld)",
                   (long long)K);
   VITMI_CHECK_ARG(N <= (int64_t)0x7fffffff && K <= (int64_t)0x7fffffff, "layerscale_bwd: N and K must be < 2^31");
-  VITMI_CHECK_ARG(aligned16(w) && aligned16(dw), "layerscale_bwd: w and dw must be 16-byte aligned");
+  VITMI_CHECK_ARG(aligned_to(w, 16) && aligned_to(dw, 16), "layerscale_bwd: w and dw must be 16-byte aligned");
   if (!dgamma && !scale_grads) return VITMI_OK;   // frozen gamma, gradients in temporaries: nothing to do
   const hipStream_t s = (hipStream_t)stream;
   const bool wide = K > 1024;                     // a block per row from 4 KiB rows on, a wave below
   const dim3 grid((unsigned)(wide ? N : (N + 3) / 4));
   const double bytes = (dw ? 4.0 * N * K : 0.0) * ((dgamma ? 2 : 1) + (scale_grads ? 1 : 0));
-#define VITMI_LS_LAUNCH(WPR, DOT, SCALE)                                                                         \
-  do {                                                                                                           \
-    hipLaunchKernelGGL((layerscale_bwd_kernel<WPR, DOT, SCALE>), grid, dim3(256), 0, s, N, K, w, bias, gamma, dw, \
-                       db, dgamma);                                                                              \
-    VITMI_STAT((layerscale_bwd_kernel<WPR, DOT, SCALE>), dgamma ? 2.0 * N * K : 0.0, bytes);                     \
-  } while (0)
-  if (wide) {
-    if (dgamma && scale_grads) VITMI_LS_LAUNCH(4, true, true);
-    else if (dgamma) VITMI_LS_LAUNCH(4, true, false);
-    else VITMI_LS_LAUNCH(4, false, true);
-  } else {
-    if (dgamma && scale_grads) VITMI_LS_LAUNCH(1, true, true);
-    else if (dgamma) VITMI_LS_LAUNCH(1, true, false);
-    else VITMI_LS_LAUNCH(1, false, true);
-  }
-#undef VITMI_LS_LAUNCH
+  // [wide][dgamma and scale_grads, dgamma alone, scale_grads alone]
+  static constexpr decltype(&layerscale_bwd_kernel<1, true, true>) kern[2][3] = {
+      {layerscale_bwd_kernel<1, true, true>, layerscale_bwd_kernel<1, true, false>,
+       layerscale_bwd_kernel<1, false, true>},
+      {layerscale_bwd_kernel<4, true, true>, layerscale_bwd_kernel<4, true, false>,
+       layerscale_bwd_kernel<4, false, true>}};
+  launch(kern[wide][dgamma ? (scale_grads ? 0 : 1) : 2], grid, dim3(256), s, dgamma ? 2.0 * N * K : 0.0, bytes, N, K, w,
+         bias, gamma, dw, db, dgamma);
   VITMI_LAUNCH_CHECK("layerscale_bwd");
   return VITMI_OK;
 }
@@ -224,20 +206,12 @@ extern "C" int vitmi_layerscale_apply(int64_t M, int64_t N, const float* x, int6
   VITMI_CHECK_ARG(M >= 0 && N >= 0, "layerscale_apply: negative size");
   VITMI_CHECK_ARG(N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= N && ldy >= N,
                   "layerscale_apply: N and leading dims must be multiples of 4");
-  VITMI_CHECK_ARG(aligned16(x) && aligned16(gamma) && ((uintptr_t)y % 8) == 0, "layerscale_apply: alignment");
+  VITMI_CHECK_ARG(aligned_to(x, 16) && aligned_to(gamma, 16) && aligned_to(y, 8), "layerscale_apply: alignment");
   if (M == 0 || N == 0) return VITMI_OK;
-  int64_t blocks = (M * (N / 4) + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  const hipStream_t s = (hipStream_t)stream;
-  if (y_dtype == VITMI_F32) {
-    hipLaunchKernelGGL(layerscale_apply_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, M, N, x, ldx, gamma,
-                       (float*)y, ldy);
-    VITMI_STAT(layerscale_apply_kernel<float>, 0, 8.0 * M * N);
-  } else {
-    hipLaunchKernelGGL(layerscale_apply_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, s, M, N, x, ldx, gamma,
-                       (bf16*)y, ldy);
-    VITMI_STAT(layerscale_apply_kernel<bf16>, 0, 6.0 * M * N);
-  }
+  const bool f32 = y_dtype == VITMI_F32;
+  launch(f32 ? untyped(layerscale_apply_kernel<float>) : untyped(layerscale_apply_kernel<bf16>),
+         dim3(grid_cap(M * (N / 4))), dim3(256), (hipStream_t)stream, 0, (f32 ? 8.0 : 6.0) * M * N, M, N, x, ldx, gamma,
+         y, ldy);
   VITMI_LAUNCH_CHECK("layerscale_apply");
   return VITMI_OK;
 }
@@ -254,16 +228,15 @@ extern "C" int vitmi_layerscale_dgamma(int64_t M, int64_t N, const float* dy, in
   VITMI_CHECK_ARG(M >= 0 && N >= 0, "layerscale_dgamma: negative size");
   VITMI_CHECK_ARG(N % 4 == 0 && lddy % 4 == 0 && ldx % 4 == 0 && lddy >= N && ldx >= N,
                   "layerscale_dgamma: N and leading dims must be multiples of 4");
-  VITMI_CHECK_ARG(aligned16(dy) && aligned16(x), "layerscale_dgamma: alignment");
+  VITMI_CHECK_ARG(aligned_to(dy, 16) && aligned_to(x, 16), "layerscale_dgamma: alignment");
   if (M == 0 || N == 0) return VITMI_OK;
-  VITMI_CHECK_ARG(workspace && aligned16(workspace) && ws_bytes >= vitmi_layerscale_dgamma_workspace_size(M, N),
+  VITMI_CHECK_ARG(workspace && aligned_to(workspace, 16) && ws_bytes >= vitmi_layerscale_dgamma_workspace_size(M, N),
                   "layerscale_dgamma: workspace too small");
   const int Z = dgamma_splits(M, N);
   const int64_t rows_per = (M + Z - 1) / Z;
   const hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(layerscale_dgamma_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)Z), dim3(256), 0, s, M, N,
-                     dy, lddy, x, ldx, (float*)workspace, rows_per);
-  VITMI_STAT(layerscale_dgamma_kernel, 2.0 * M * N, 8.0 * M * N);
+  launch(layerscale_dgamma_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)Z), dim3(256), s, 2.0 * M * N,
+         8.0 * M * N, M, N, dy, lddy, x, ldx, (float*)workspace, rows_per);
   VITMI_LAUNCH_CHECK("layerscale_dgamma");
   return fold_rows((const float*)workspace, Z, N, N, dgamma, s);
 }

@@ -377,7 +377,7 @@ extern "C" int vitmi_softmax_xent(int B, int C, const float* logits, int64_t ldl
   if (metrics) {
     VITMI_CHECK_ARG(label_a != nullptr, "softmax_xent: metrics are scored against label_a, which is null");
     VITMI_CHECK_ARG(topk >= 1, "softmax_xent: topk must be >= 1 with metrics");
-    VITMI_CHECK_ARG((uintptr_t)metrics % 16 == 0, "softmax_xent: the metrics record must be 16-byte aligned");
+    VITMI_CHECK_ARG(aligned_to(metrics, 16), "softmax_xent: the metrics record must be 16-byte aligned");
   }
   const bool finalize = loss || metrics;
   const bool need_ws = metrics || (loss && !row_loss);
@@ -385,7 +385,7 @@ extern "C" int vitmi_softmax_xent(int B, int C, const float* logits, int64_t ldl
     VITMI_CHECK_ARG(workspace != nullptr && workspace_bytes >= vitmi_softmax_xent_workspace_size(B),
                     "softmax_xent: workspace too small (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0,
                     vitmi_softmax_xent_workspace_size(B));
-    VITMI_CHECK_ARG((uintptr_t)workspace % 4 == 0, "softmax_xent: the workspace must be 4-byte aligned");
+    VITMI_CHECK_ARG(aligned_to(workspace, 4), "softmax_xent: the workspace must be 4-byte aligned");
   }
   float* rows = row_loss ? row_loss : (finalize ? (float*)workspace : nullptr);
   uint8_t* flags = metrics ? (uint8_t*)workspace + ((size_t)B * 4 + 15) / 16 * 16 : nullptr;
@@ -393,24 +393,22 @@ extern "C" int vitmi_softmax_xent(int B, int C, const float* logits, int64_t ldl
   XentArgs a{B, C, logits, ldl, label_a, label_b, lam, soft, lds, smoothing, topk, rows, dlogits, lddl, flags,
              1.f / (float)B};
   // 16-byte row accesses need every row base of every array the kernel touches aligned
-  bool vec = C % 4 == 0 && (uintptr_t)logits % 16 == 0 && ldl % 4 == 0;
-  if (soft) vec = vec && (uintptr_t)soft % 16 == 0 && lds % 4 == 0;
-  if (dlogits) vec = vec && (uintptr_t)dlogits % 16 == 0 && lddl % 4 == 0;
+  const bool vec = C % 4 == 0 && aligned_to(logits, 16) && ldl % 4 == 0 && aligned_to(soft, 16) &&
+                   (!soft || lds % 4 == 0) && aligned_to(dlogits, 16) && (!dlogits || lddl % 4 == 0);
   // one row per wave; small batches take one wave per block so the rows spread over the CUs
   const int rpb = B >= 2048 ? 4 : 1;
   const dim3 grid((unsigned)((B + rpb - 1) / rpb)), block(64 * rpb);
   void (*kern)(XentArgs) = vec ? (soft ? softmax_xent_kernel<4, true> : softmax_xent_kernel<4, false>)
                                : (soft ? softmax_xent_kernel<1, true> : softmax_xent_kernel<1, false>);
-  hipLaunchKernelGGL(kern, grid, block, 0, (hipStream_t)stream, a);
-  VITMI_LAUNCH_CHECK("softmax_xent");
   // the logits once (a row past the registers a second time, from L2), the dense target, the gradient
   const double n = (double)B * C;
-  VITMI_STAT(kern, 0, n * 4 * (1 + (soft ? 1 : 0) + (dlogits ? 1 : 0)) + (double)B * 16);
+  launch(kern, grid, block, (hipStream_t)stream, 0, n * 4 * (1 + (soft ? 1 : 0) + (dlogits ? 1 : 0)) + (double)B * 16,
+         a);
+  VITMI_LAUNCH_CHECK("softmax_xent");
   if (finalize) {
-    hipLaunchKernelGGL(xent_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, B, (const float*)rows,
-                       (const uint8_t*)flags, loss, (ClassRec*)metrics);
+    launch(xent_finalize_kernel, dim3(1), dim3(256), (hipStream_t)stream, 0, (double)B * 5 + (metrics ? 64.0 : 0.0) + 4,
+           B, (const float*)rows, (const uint8_t*)flags, loss, (ClassRec*)metrics);
     VITMI_LAUNCH_CHECK("softmax_xent finalize");
-    VITMI_STAT(xent_finalize_kernel, 0, (double)B * 5 + (metrics ? 64.0 : 0.0) + 4);
   }
   return VITMI_OK;
 }
@@ -424,16 +422,15 @@ extern "C" int vitmi_mix_batch(int B, int C, int H, int W, const float* img, con
   VITMI_CHECK_ARG(hw <= 0x7fffffff && (int64_t)B * C <= 0x7fffffff, "mix_batch: plane or plane count too large");
   const int64_t n = (int64_t)B * C * hw;
   VITMI_CHECK_ARG(out + n <= img || img + n <= out, "mix_batch: out must not alias img");
-  const bool vec = W % 4 == 0 && (uintptr_t)img % 16 == 0 && (uintptr_t)out % 16 == 0;
+  const bool vec = W % 4 == 0 && aligned_to(img, 16) && aligned_to(out, 16);
   const int64_t groups = vec ? hw / 4 : hw;
   const int64_t chunks = (groups + MIX_THREADS * MIX_U - 1) / (MIX_THREADS * MIX_U);
   const int64_t blocks = chunks * B * C;
   VITMI_CHECK_ARG(blocks <= 0x7fffffff, "mix_batch: batch too large for one launch");
   MixArgs a{B, C, H, W, img, out, perm, lam, box, (uint32_t)chunks};
   void (*kern)(MixArgs) = vec ? mix_batch_kernel<4> : mix_batch_kernel<1>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(MIX_THREADS), 0, (hipStream_t)stream, a);
-  VITMI_LAUNCH_CHECK("mix_batch");
   // the batch read as itself and as the partner, written once; the three tables
-  VITMI_STAT(kern, 0, (double)n * 12 + (double)B * 24);
+  launch(kern, dim3((unsigned)blocks), dim3(MIX_THREADS), (hipStream_t)stream, 0, (double)n * 12 + (double)B * 24, a);
+  VITMI_LAUNCH_CHECK("mix_batch");
   return VITMI_OK;
 }

@@ -293,26 +293,17 @@ extern "C" int vitmi_adam_step(int64_t n, float* p, const float* g, float* m, fl
   VITMI_CHECK_ARG(n >= 0, "adam_step: n < 0");
   if (n == 0) return VITMI_OK;
   VITMI_CHECK_ARG(p && g && m && v, "adam_step: null pointer");
-  VITMI_CHECK_ARG(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0,
+  VITMI_CHECK_ARG(aligned_to(p, 16) && aligned_to(g, 16) && aligned_to(m, 16) && aligned_to(v, 16),
                   "adam_step: fp32 buffers must be 16-byte aligned");
-  VITMI_CHECK_ARG(!p_lp || (uintptr_t)p_lp % 8 == 0, "adam_step: bf16 shadow must be 8-byte aligned");
+  VITMI_CHECK_ARG(aligned_to(p_lp, 8), "adam_step: bf16 shadow must be 8-byte aligned");
   VITMI_CHECK_ARG(beta_1 >= 0.0 && beta_1 < 1.0 && beta_2 >= 0.0 && beta_2 < 1.0 && epsilon >= 0.f,
                   "adam_step: bad hyper-parameters");
   // (1 - beta) in double then rounded once, as Keras does with its Python-float hyper-parameters
   AdamArgs a{alpha, (float)(1.0 - beta_1), (float)(1.0 - beta_2), epsilon, grad_scale};
-  const int64_t work = (n / 4) > 0 ? (n / 4) : 1;
-  int64_t blocks = (work + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  if (p_lp)
-    hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v,
-                       (bf16*)p_lp, a);
-  else
-    hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v,
-                       (bf16*)nullptr, a);
-  VITMI_LAUNCH_CHECK("adam_step");
   // p, g, m, v read; p, m, v (+ the bf16 shadow) written
-  if (p_lp) VITMI_STAT(adam_kernel<true>, 0, (double)n * 30);
-  else VITMI_STAT(adam_kernel<false>, 0, (double)n * 28);
+  launch(p_lp ? adam_kernel<true> : adam_kernel<false>, dim3(grid_cap(n / 4)), dim3(256), (hipStream_t)stream, 0,
+         (double)n * (p_lp ? 30 : 28), n, p, g, m, v, (bf16*)p_lp, a);
+  VITMI_LAUNCH_CHECK("adam_step");
   return VITMI_OK;
 }
 
@@ -324,15 +315,14 @@ extern "C" int vitmi_grad_sumsq(int64_t n, const float* g, double* partials, vit
   VITMI_CHECK_ARG(n >= 0, "grad_sumsq: n < 0");
   if (n == 0) return VITMI_OK;
   VITMI_CHECK_ARG(g && partials, "grad_sumsq: null pointer");
-  VITMI_CHECK_ARG((uintptr_t)g % 16 == 0, "grad_sumsq: the gradient buffer must be 16-byte aligned");
-  VITMI_CHECK_ARG((uintptr_t)partials % 8 == 0, "grad_sumsq: partials must be 8-byte aligned");
+  VITMI_CHECK_ARG(aligned_to(g, 16), "grad_sumsq: the gradient buffer must be 16-byte aligned");
+  VITMI_CHECK_ARG(aligned_to(partials, 8), "grad_sumsq: partials must be 8-byte aligned");
   const size_t chunks = vitmi_grad_sumsq_partials(n);
   VITMI_CHECK_ARG(chunks <= 0x7fffffffu, "grad_sumsq: n too large for one launch");
-  hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)chunks), dim3(SUMSQ_THREADS), 0, (hipStream_t)stream, n, g,
-                     partials);
-  VITMI_LAUNCH_CHECK("grad_sumsq");
   // g read once; one double per chunk written
-  VITMI_STAT(grad_sumsq_kernel, 0, (double)n * 4 + (double)chunks * 8);
+  launch(grad_sumsq_kernel, dim3((unsigned)chunks), dim3(SUMSQ_THREADS), (hipStream_t)stream, 0,
+         (double)n * 4 + (double)chunks * 8, n, g, partials);
+  VITMI_LAUNCH_CHECK("grad_sumsq");
   return VITMI_OK;
 }
 
@@ -340,13 +330,13 @@ extern "C" int vitmi_clip_finalize(int64_t n_partials, const double* partials, f
                                    int skip_nonfinite, void* ctl, vitmi_stream_t stream) {
   VITMI_CHECK_ARG(n_partials >= 0, "clip_finalize: n_partials < 0");
   VITMI_CHECK_ARG(ctl && (partials || n_partials == 0), "clip_finalize: null pointer");
-  VITMI_CHECK_ARG((uintptr_t)partials % 8 == 0, "clip_finalize: partials must be 8-byte aligned");
-  VITMI_CHECK_ARG((uintptr_t)ctl % 16 == 0, "clip_finalize: the clip record must be 16-byte aligned");
+  VITMI_CHECK_ARG(aligned_to(partials, 8), "clip_finalize: partials must be 8-byte aligned");
+  VITMI_CHECK_ARG(aligned_to(ctl, 16), "clip_finalize: the clip record must be 16-byte aligned");
   VITMI_CHECK_ARG(clip_norm >= 0.f, "clip_finalize: clip_norm must be >= 0 (0 = off)");
-  hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(SUMSQ_THREADS), 0, (hipStream_t)stream, n_partials, partials,
-                     grad_scale, clip_norm, skip_nonfinite, (ClipCtl*)ctl);
+  launch(clip_finalize_kernel, dim3(1), dim3(SUMSQ_THREADS), (hipStream_t)stream, 0,
+         (double)n_partials * 8 + 2 * sizeof(ClipCtl), n_partials, partials, grad_scale, clip_norm, skip_nonfinite,
+         (ClipCtl*)ctl);
   VITMI_LAUNCH_CHECK("clip_finalize");
-  VITMI_STAT(clip_finalize_kernel, 0, (double)n_partials * 8 + 2 * sizeof(ClipCtl));
   return VITMI_OK;
 }
 
@@ -356,27 +346,19 @@ extern "C" int vitmi_adam_step_ctl(int64_t n, float* p, const float* g, float* m
   VITMI_CHECK_ARG(n >= 0, "adam_step_ctl: n < 0");
   if (n == 0) return VITMI_OK;
   VITMI_CHECK_ARG(p && g && m && v, "adam_step_ctl: null pointer");
-  VITMI_CHECK_ARG(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0,
+  VITMI_CHECK_ARG(aligned_to(p, 16) && aligned_to(g, 16) && aligned_to(m, 16) && aligned_to(v, 16),
                   "adam_step_ctl: fp32 buffers must be 16-byte aligned");
-  VITMI_CHECK_ARG(!p_lp || (uintptr_t)p_lp % 8 == 0, "adam_step_ctl: bf16 shadow must be 8-byte aligned");
-  VITMI_CHECK_ARG((uintptr_t)ctl % 16 == 0, "adam_step_ctl: the clip record must be 16-byte aligned");
+  VITMI_CHECK_ARG(aligned_to(p_lp, 8), "adam_step_ctl: bf16 shadow must be 8-byte aligned");
+  VITMI_CHECK_ARG(aligned_to(ctl, 16), "adam_step_ctl: the clip record must be 16-byte aligned");
   VITMI_CHECK_ARG(beta_1 >= 0.0 && beta_1 < 1.0 && beta_2 >= 0.0 && beta_2 < 1.0 && epsilon >= 0.f,
                   "adam_step_ctl: bad hyper-parameters");
   VITMI_CHECK_ARG(weight_decay >= 0.f, "adam_step_ctl: weight_decay must be >= 0");
   AdamArgs a{alpha, (float)(1.0 - beta_1), (float)(1.0 - beta_2), epsilon, grad_scale};
-  const int64_t work = (n / 4) > 0 ? (n / 4) : 1;
-  int64_t blocks = (work + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  if (p_lp)
-    hipLaunchKernelGGL(adam_ctl_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v,
-                       (bf16*)p_lp, a, weight_decay, lr, decay_mask, (const ClipCtl*)ctl);
-  else
-    hipLaunchKernelGGL(adam_ctl_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, p, g, m,
-                       v, (bf16*)nullptr, a, weight_decay, lr, decay_mask, (const ClipCtl*)ctl);
-  VITMI_LAUNCH_CHECK("adam_step_ctl");
   // as adam_step, plus the mask bytes and the record (a skipped step moves less: not known here)
   const double extra = (decay_mask && weight_decay != 0.f ? (double)((n + 63) / 64) : 0.0) + (ctl ? 16.0 : 0.0);
-  if (p_lp) VITMI_STAT(adam_ctl_kernel<true>, 0, (double)n * 30 + extra);
-  else VITMI_STAT(adam_ctl_kernel<false>, 0, (double)n * 28 + extra);
+  launch(p_lp ? adam_ctl_kernel<true> : adam_ctl_kernel<false>, dim3(grid_cap(n / 4)), dim3(256), (hipStream_t)stream,
+         0, (double)n * (p_lp ? 30 : 28) + extra, n, p, g, m, v, (bf16*)p_lp, a, weight_decay, lr, decay_mask,
+         (const ClipCtl*)ctl);
+  VITMI_LAUNCH_CHECK("adam_step_ctl");
   return VITMI_OK;
 }

@@ -157,12 +157,6 @@ __global__ void tokens_pos_keep_bwd_kernel(int B, int np, int K, int D, const fl
   if (dcls && n == 0) dcls[d] += s;
 }
 
-static unsigned grid_for(int64_t work, int per_block = 256) {
-  int64_t g = (work + per_block - 1) / per_block;
-  if (g > 8192) g = 8192;
-  return (unsigned)(g < 1 ? 1 : g);
-}
-
 }  // namespace vitmi
 
 using namespace vitmi;
@@ -174,8 +168,8 @@ extern "C" int vitmi_patch_keep(int B, int np, int K, uint32_t seed, uint32_t si
                                 vitmi_stream_t stream) {
   PATCHDROP_CHECK_GEOM("patch_keep");
   VITMI_CHECK_ARG(keep && slot, "patch_keep: null pointer");
-  hipLaunchKernelGGL(patch_keep_kernel, dim3((unsigned)B), dim3(KEEP_THREADS), 0, (hipStream_t)stream, np, K, seed,
-                     site, keep, slot);
+  launch(patch_keep_kernel, dim3((unsigned)B), dim3(KEEP_THREADS), (hipStream_t)stream, no_stat, np, K, seed, site,
+         keep, slot);
   VITMI_LAUNCH_CHECK("patch_keep");
   return VITMI_OK;
 }
@@ -190,14 +184,9 @@ extern "C" int vitmi_patch_im2col_keep(int dtype, int B, int C, int S, int P, in
   VITMI_CHECK_ARG(dtype == VITMI_BF16 || dtype == VITMI_F32, "im2col_keep: bad dtype");
   const int64_t Kc = (int64_t)C * P * P, rows = (int64_t)B * K;
   VITMI_CHECK_ARG(Kc / 4 <= 1024 && rows < 0x7fffffff, "im2col_keep: C*P*P must be <= 4096");
-  hipStream_t s = (hipStream_t)stream;
   const dim3 block((unsigned)((Kc / 4 + 63) / 64 * 64));
-  if (dtype == VITMI_BF16)
-    hipLaunchKernelGGL(im2col_keep_kernel<bf16>, dim3((unsigned)rows), block, 0, s, img, (bf16*)patches, C, S, P, K,
-                       keep);
-  else
-    hipLaunchKernelGGL(im2col_keep_kernel<float>, dim3((unsigned)rows), block, 0, s, img, (float*)patches, C, S, P, K,
-                       keep);
+  launch(dtype == VITMI_BF16 ? untyped(im2col_keep_kernel<bf16>) : untyped(im2col_keep_kernel<float>),
+         dim3((unsigned)rows), block, (hipStream_t)stream, no_stat, img, patches, C, S, P, K, keep);
   VITMI_LAUNCH_CHECK("im2col_keep");
   return VITMI_OK;
 }
@@ -208,8 +197,8 @@ extern "C" int vitmi_tokens_assemble_keep(int B, int np, int K, int D, const flo
   VITMI_CHECK_ARG(D > 0 && D % 4 == 0, "tokens_assemble_keep: D %% 4 != 0");
   VITMI_CHECK_ARG(tok && keep && x, "tokens_assemble_keep: null pointer");
   const int64_t work = (int64_t)B * (K + 1) * D / 4;
-  hipLaunchKernelGGL(tokens_assemble_keep_kernel, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream, B, np, K,
-                     D, tok, cls, pos, keep, x);
+  launch(tokens_assemble_keep_kernel, dim3(grid_cap(work)), dim3(256), (hipStream_t)stream, no_stat, B, np, K, D, tok,
+         cls, pos, keep, x);
   VITMI_LAUNCH_CHECK("tokens_assemble_keep");
   return VITMI_OK;
 }
@@ -225,8 +214,8 @@ extern "C" int vitmi_tokens_assemble_keep_bwd(int B, int np, int K, int D, const
     if (int rc = vitmi_tokens_assemble_bwd(B, K, D, dx, dtok, dtok_lp, nullptr, nullptr, stream)) return rc;
   if (dcls || dpos) {
     const int64_t work = (int64_t)(np + 1) * D;
-    hipLaunchKernelGGL(tokens_pos_keep_bwd_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, B, np, K, D, dx, slot, dcls, dpos);
+    launch(tokens_pos_keep_bwd_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), (hipStream_t)stream, no_stat, B,
+           np, K, D, dx, slot, dcls, dpos);
   }
   VITMI_LAUNCH_CHECK("tokens_assemble_keep_bwd");
   return VITMI_OK;

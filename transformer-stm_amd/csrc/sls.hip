@@ -89,10 +89,8 @@ extern "C" int vitmi_sls_preprocess(int n, int H, int W, const void* src, int64_
   VITMI_CHECK_ARG(src && xofs && xw && yofs && yw && out, "sls_preprocess: null pointer");
   VITMI_CHECK_ARG(row_bytes >= 3LL * W && img_bytes >= row_bytes * H, "sls_preprocess: bad source layout");
   const int64_t total = (int64_t)n * Ho * Wo;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(sls_preprocess_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, H, W,
-                     (const uint8_t*)src, img_bytes, row_bytes, bgr, Ho, Wo, xofs, xw, yofs, yw, out);
+  launch(sls_preprocess_kernel, dim3(grid_cap(total, 256, 16384)), dim3(256), (hipStream_t)stream, no_stat, n, H, W,
+         (const uint8_t*)src, img_bytes, row_bytes, bgr, Ho, Wo, xofs, xw, yofs, yw, out);
   VITMI_LAUNCH_CHECK("sls_preprocess");
   return VITMI_OK;
 }
@@ -126,16 +124,11 @@ extern "C" int vitmi_gather_rows(int64_t n, int64_t row_bytes, const void* src, 
   VITMI_CHECK_ARG(n >= 0 && row_bytes > 0, "gather_rows: bad sizes");
   if (n == 0) return VITMI_OK;
   VITMI_CHECK_ARG(src && idx && dst, "gather_rows: null pointer");
-  const bool vec = row_bytes % 16 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
-  const int64_t total = vec ? n * (row_bytes / 16) : n * row_bytes;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  if (vec)
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, row_bytes / 16,
-                       (const uint4*)src, n_src, idx, (uint4*)dst);
-  else
-    hipLaunchKernelGGL(gather_rows_b_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, row_bytes,
-                       (const uint8_t*)src, n_src, idx, (uint8_t*)dst);
+  const bool vec = row_bytes % 16 == 0 && aligned_to(src, 16) && aligned_to(dst, 16);
+  const int64_t unit = vec ? 16 : 1;   // bytes per thread and step
+  launch(vec ? untyped(gather_rows_kernel) : untyped(gather_rows_b_kernel),
+         dim3(grid_cap(n * (row_bytes / unit), 256, 16384)), dim3(256), (hipStream_t)stream, no_stat, n, row_bytes / unit,
+         src, n_src, idx, dst);
   VITMI_LAUNCH_CHECK("gather_rows");
   return VITMI_OK;
 }

@@ -106,11 +106,6 @@ __global__ __launch_bounds__(256) void split_f8_batch_kernel(SplitBatch b) {
   }
 }
 
-static unsigned grid_of(int64_t items) {
-  int64_t b = (items + 255) / 256;
-  return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
-
 }  // namespace vitmi
 
 using namespace vitmi;
@@ -124,12 +119,12 @@ extern "C" int vitmi_split_bf16x3(int64_t rows, int64_t K, const float* src, int
   VITMI_CHECK_ARG(!hi_copy || (ld_copy >= K && ld_copy % 4 == 0), "split_bf16x3: bad ld_copy");
   if (rows == 0) return VITMI_OK;
   VITMI_CHECK_ARG(src && dst, "split_bf16x3: null pointer");
-  VITMI_CHECK_ARG(((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 8) == 0 && ((uintptr_t)hi_copy % 8) == 0,
+  VITMI_CHECK_ARG(aligned_to(src, 16) && aligned_to(dst, 8) && aligned_to(hi_copy, 8),
                   "split_bf16x3: src 16-byte, dst/copy 8-byte alignment required");
-  hipLaunchKernelGGL(split3_kernel, dim3(grid_of(rows * K / 4)), dim3(256), 0, (hipStream_t)stream, rows, K, src,
-                     ld_src, (bf16*)dst, ld_dst, pattern, (bf16*)hi_copy, ld_copy);
+  launch(split3_kernel, dim3(grid_cap(rows * K / 4)), dim3(256), (hipStream_t)stream, 0,
+         (double)rows * K * (4 + 6 + (hi_copy ? 2 : 0)), rows, K, src, ld_src, (bf16*)dst, ld_dst, pattern,
+         (bf16*)hi_copy, ld_copy);
   VITMI_LAUNCH_CHECK("split_bf16x3");
-  VITMI_STAT(split3_kernel, 0, (double)rows * K * (4 + 6 + (hi_copy ? 2 : 0)));
   return VITMI_OK;
 }
 
@@ -144,16 +139,16 @@ extern "C" int vitmi_split_bf16f8_weights_mixed(int n, const float* const* srcs,
     VITMI_CHECK_ARG(b.pat[j] == 1 || b.pat[j] == 3, "split_bf16f8_weights: weight %d: pattern must be 1 or 3", j);
     VITMI_CHECK_ARG(rows[j] > 0 && K[j] > 0 && K[j] % (b.pat[j] == 3 ? 128 : 64) == 0,
                     "split_bf16f8_weights: weight %d: K %% %d and rows", j, b.pat[j] == 3 ? 128 : 64);
-    VITMI_CHECK_ARG(srcs[j] && dsts[j] && ((uintptr_t)srcs[j] % 16) == 0 && ((uintptr_t)dsts[j] % 16) == 0,
+    VITMI_CHECK_ARG(srcs[j] && dsts[j] && aligned_to(srcs[j], 16) && aligned_to(dsts[j], 16),
                     "split_bf16f8_weights: weight %d: null or unaligned pointer", j);
     b.src[j] = srcs[j];
     b.dst[j] = (bf16*)dsts[j];
     b.K[j] = K[j];
     b.start[j + 1] = b.start[j] + rows[j] * K[j] / 4;
   }
-  hipLaunchKernelGGL(split_f8_batch_kernel, dim3(grid_of(b.start[n])), dim3(256), 0, (hipStream_t)stream, b);
+  launch(split_f8_batch_kernel, dim3(grid_cap(b.start[n])), dim3(256), (hipStream_t)stream, 0,
+         (double)b.start[n] * 4 * 8, b);
   VITMI_LAUNCH_CHECK("split_bf16f8_weights");
-  VITMI_STAT(split_f8_batch_kernel, 0, (double)b.start[n] * 4 * 8);
   return VITMI_OK;
 }
 
@@ -174,11 +169,11 @@ extern "C" int vitmi_split_bf16f8(int64_t rows, int64_t K, const float* src, int
   VITMI_CHECK_ARG(!hi_copy || (ld_copy >= K && ld_copy % 4 == 0), "split_bf16f8: bad ld_copy");
   if (rows == 0) return VITMI_OK;
   VITMI_CHECK_ARG(src && dst, "split_bf16f8: null pointer");
-  VITMI_CHECK_ARG(((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 8) == 0 && ((uintptr_t)hi_copy % 8) == 0,
+  VITMI_CHECK_ARG(aligned_to(src, 16) && aligned_to(dst, 8) && aligned_to(hi_copy, 8),
                   "split_bf16f8: src 16-byte, dst/copy 8-byte alignment required");
-  hipLaunchKernelGGL(split_f8_kernel, dim3(grid_of(rows * K / 4)), dim3(256), 0, (hipStream_t)stream, rows, K, src,
-                     ld_src, (bf16*)dst, ld_dst, pattern, (bf16*)hi_copy, ld_copy);
+  launch(split_f8_kernel, dim3(grid_cap(rows * K / 4)), dim3(256), (hipStream_t)stream, 0,
+         (double)rows * K * (4 + 4 + (hi_copy ? 2 : 0)), rows, K, src, ld_src, (bf16*)dst, ld_dst, pattern,
+         (bf16*)hi_copy, ld_copy);
   VITMI_LAUNCH_CHECK("split_bf16f8");
-  VITMI_STAT(split_f8_kernel, 0, (double)rows * K * (4 + 4 + (hi_copy ? 2 : 0)));
   return VITMI_OK;
 }
