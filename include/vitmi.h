@@ -498,7 +498,10 @@ int vitmi_conv_col2im(int dtype, int B, int H, int W, int C, int kh, int kw, int
  * the unbiased n/(n-1) estimate, as Keras' fused BN and torch's BatchNorm2d do); training == 0 -> the
  * moving statistics normalise (Keras inference).  x/dx rows as above (cls row skipped via
  * x_off), y rows b*y_img + y_off + hw of y [..][ldy] (y_dtype).  z [B*H*W][C], mean/rstd [C]
- * are saved for the backward.  C % 4 == 0 and 1024 % C == 0. */
+ * are saved for the backward.  C % 4 == 0 and 1024 % C == 0.  Every pitch is a multiple of 4 and >= C,
+ * every offset >= 0, y_dtype / dy_dtype VITMI_F32 or VITMI_BF16; the fp32 pointers the kernels read or
+ * write four channels at a time (x, w, gamma, beta, z, mean, rstd, dx, the workspace; dx of
+ * vitmi_conv_col2im and of vitmi_avgpool3_bwd, x of vitmi_avgpool3_fwd) must be 16-byte aligned. */
 size_t vitmi_dwconv_bn_workspace_size(int B, int H, int W, int C);
 int vitmi_dwconv_bn_fwd(int B, int H, int W, int C, const float* x, int64_t ldx, int64_t x_img, int64_t x_off,
                         const float* w, const float* gamma, const float* beta, float eps, float momentum,

@@ -528,6 +528,7 @@ extern "C" int vitmi_conv_col2im(int dtype, int B, int H, int W, int C, int kh, 
   if (int rc = make_geo(g, B, H, W, C, kh, kw, s, pad_top, pad_left, Ho, Wo, ldx, img_stride, row_off)) return rc;
   VITMI_CHECK_ARG(dpatches && dx, "conv_col2im: null pointer");
   VITMI_CHECK_ARG(C % 4 == 0 && ldx % 4 == 0 && Kp >= kh * kw * C, "conv_col2im: C %% 4 == 0 required");
+  VITMI_CHECK_ARG(aligned_to(dx, 16), "conv_col2im: dx must be 16-byte aligned");
   const int64_t work = (int64_t)B * H * W * (C / 4);
   launch(dtype == VITMI_BF16 ? untyped(conv_col2im_kernel<bf16>) : untyped(conv_col2im_kernel<float>),
          dim3(grid_cap(work, 256, CVT_BLOCKS)), dim3(256), (hipStream_t)stream, no_stat, g, dpatches, Kp, dx,
@@ -561,7 +562,12 @@ extern "C" int vitmi_dwconv_bn_fwd(int B, int H, int W, int C, const float* x, i
   if (int rc = make_dw(g, B, H, W, C, ldx, x_img, x_off)) return rc;
   VITMI_CHECK_ARG(x && wt && gamma && beta && z && mean && rstd && y, "dwconv_bn_fwd: null pointer");
   VITMI_CHECK_ARG(workspace && ws_bytes >= vitmi_dwconv_bn_workspace_size(B, H, W, C), "dwconv_bn_fwd: workspace");
-  VITMI_CHECK_ARG(ldy % 4 == 0 && y_img >= (int64_t)H * W + y_off, "dwconv_bn_fwd: bad output layout");
+  VITMI_CHECK_ARG(ldy % 4 == 0 && ldy >= C && y_img >= (int64_t)H * W + y_off && y_off >= 0,
+                  "dwconv_bn_fwd: bad output layout");
+  VITMI_CHECK_ARG(y_dtype == VITMI_BF16 || y_dtype == VITMI_F32, "dwconv_bn_fwd: bad dtype");
+  VITMI_CHECK_ARG(aligned_to(x, 16) && aligned_to(wt, 16) && aligned_to(gamma, 16) && aligned_to(beta, 16) &&
+                      aligned_to(z, 16) && aligned_to(mean, 16) && aligned_to(rstd, 16) && aligned_to(workspace, 16),
+                  "dwconv_bn_fwd: x, wt, gamma, beta, z, mean, rstd and the workspace must be 16-byte aligned");
   VITMI_CHECK_ARG(training || (run_mean && run_var), "dwconv_bn_fwd: inference needs the moving statistics");
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = (int64_t)B * H * W;
@@ -589,7 +595,12 @@ extern "C" int vitmi_dwconv_bn_bwd(int B, int H, int W, int C, const void* dy, i
   if (int rc = make_dw(g, B, H, W, C, ldx, x_img, x_off)) return rc;
   VITMI_CHECK_ARG(dy && x && wt && gamma && z && mean && rstd && dx && dwt, "dwconv_bn_bwd: null pointer");
   VITMI_CHECK_ARG(workspace && ws_bytes >= vitmi_dwconv_bn_workspace_size(B, H, W, C), "dwconv_bn_bwd: workspace");
-  VITMI_CHECK_ARG(lddy % 4 == 0 && dy_img >= (int64_t)H * W + dy_off, "dwconv_bn_bwd: bad dy layout");
+  VITMI_CHECK_ARG(lddy % 4 == 0 && lddy >= C && dy_img >= (int64_t)H * W + dy_off && dy_off >= 0,
+                  "dwconv_bn_bwd: bad dy layout");
+  VITMI_CHECK_ARG(dy_dtype == VITMI_BF16 || dy_dtype == VITMI_F32, "dwconv_bn_bwd: bad dtype");
+  VITMI_CHECK_ARG(aligned_to(x, 16) && aligned_to(wt, 16) && aligned_to(gamma, 16) && aligned_to(z, 16) &&
+                      aligned_to(mean, 16) && aligned_to(rstd, 16) && aligned_to(dx, 16) && aligned_to(workspace, 16),
+                  "dwconv_bn_bwd: x, wt, gamma, z, mean, rstd, dx and the workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = (int64_t)B * H * W;
   const int G = dw_blocks(n, C);
@@ -690,6 +701,7 @@ extern "C" int vitmi_avgpool3_fwd(int B, int H, int W, int C, const float* x, in
   VITMI_CHECK_ARG(ldy % 4 == 0 && ldy >= C && y_img >= (int64_t)H * W + y_off && y_off >= 0,
                   "avgpool3_fwd: bad output layout");
   VITMI_CHECK_ARG(y_dtype == VITMI_BF16 || y_dtype == VITMI_F32, "avgpool3_fwd: bad dtype");
+  VITMI_CHECK_ARG(aligned_to(x, 16), "avgpool3_fwd: x must be 16-byte aligned");
   const int64_t work = (int64_t)B * H * W * (C / 4);
   launch(y_dtype == VITMI_BF16 ? untyped(avgpool3_fwd_kernel<bf16>) : untyped(avgpool3_fwd_kernel<float>),
          dim3(grid_cap(work, 256, CVT_BLOCKS)), dim3(256), (hipStream_t)stream, no_stat, g, x, y, ldy, y_img, y_off,
@@ -707,6 +719,7 @@ extern "C" int vitmi_avgpool3_bwd(int B, int H, int W, int C, const void* dy, in
   VITMI_CHECK_ARG(lddy % 4 == 0 && lddy >= C && dy_img >= (int64_t)H * W + dy_off && dy_off >= 0,
                   "avgpool3_bwd: bad dy layout");
   VITMI_CHECK_ARG(dy_dtype == VITMI_BF16 || dy_dtype == VITMI_F32, "avgpool3_bwd: bad dtype");
+  VITMI_CHECK_ARG(aligned_to(dx, 16), "avgpool3_bwd: dx must be 16-byte aligned");
   const int64_t work = (int64_t)B * H * W * (C / 4);
   launch(dy_dtype == VITMI_BF16 ? untyped(avgpool3_bwd_kernel<bf16>) : untyped(avgpool3_bwd_kernel<float>),
          dim3(grid_cap(work, 256, CVT_BLOCKS)), dim3(256), (hipStream_t)stream, no_stat, g, dy, lddy, dy_img, dy_off,
