@@ -588,6 +588,27 @@ int vitmi_adam_step_ctl(int64_t n, float* p, const float* g, float* m, float* v,
                         double beta_1, double beta_2, float epsilon, float grad_scale, float weight_decay, float lr,
                         const uint8_t* decay_mask, const void* ctl, vitmi_stream_t stream);
 
+/* Exponential moving average of the weights (keras.optimizers.Adam(use_ema=True, ema_momentum=)),
+ * kept inside the step, and its use for evaluation.
+ *
+ * vitmi_adam_step_ema: vitmi_adam_step_ctl (same arguments, same meaning, same rounded fp32 ops in
+ *   the same order; ctl == NULL, weight_decay == 0 and decay_mask == NULL allowed, so it covers the
+ *   plain, decayed and clipped steps) followed, per element, by
+ *     e = (mom * e) + (one_m * p_new)     (two products and one sum, each rounded; no FMA)
+ *   with mom = ema_momentum and one_m = 1.0f - mom formed once on the host in fp32 (Keras forms
+ *   1 - momentum in the variable's dtype).  mom == 0 runs the same three ops.  If ctl->skip, ema
+ *   is neither read nor written: p, m, v and ema stay bit for bit, p_lp is still written as
+ *   bf16(p).  ema: fp32, 16-byte aligned, required; ema_momentum in [0, 1).  4 B read and 4 B
+ *   written per parameter on top of the step's (38 B with the shadow, 36 B without).
+ * vitmi_ema_apply: mode 0 exchanges p and ema in place (no temporary); mode 1 writes p <- ema and
+ *   leaves ema as it is.  p_lp (optional, bf16) receives the shadow of the new p in the same pass.
+ *   p and ema fp32, 16-byte aligned; p_lp 8-byte aligned; any n >= 0. */
+int vitmi_adam_step_ema(int64_t n, float* p, const float* g, float* m, float* v, void* p_lp, float alpha,
+                        double beta_1, double beta_2, float epsilon, float grad_scale, float weight_decay, float lr,
+                        const uint8_t* decay_mask, const void* ctl, float* ema, float ema_momentum,
+                        vitmi_stream_t stream);
+int vitmi_ema_apply(int64_t n, float* p, float* ema, void* p_lp, int mode, vitmi_stream_t stream);
+
 /* The classification recipe on the device (csrc/loss.hip): softmax cross-entropy on label, mixed-pair
  * and dense soft targets with label smoothing and top-1 / top-k scoring, and the mixup / cutmix image
  * pass (timm Mixup + SoftTargetCrossEntropy; tf.keras CategoricalCrossentropy(label_smoothing=)).

@@ -208,6 +208,19 @@ __device__ __forceinline__ void adam1_ctl(const AdamArgs& a, float coef, bool de
   p = __fsub_rn(p, __fdiv_rn(__fmul_rn(m, a.alpha), den));
 }
 
+// what a skipped step still does: lp = bf16(p) over the thread's groups (and its tail element)
+__device__ __forceinline__ void shadow_only(int64_t n4, int64_t first, int64_t stride, bool tail, int64_t t,
+                                            const float* __restrict__ p, bf16* __restrict__ lp) {
+  for (int64_t i = first; i < n4; i += stride) {
+    const f32x4 pv = ld_s((const f32x4*)p + i);
+    bf16x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = from_f32<bf16>(pv[e]);
+    ((bf16x4*)lp)[i] = o;
+  }
+  if (tail) lp[t] = from_f32<bf16>(p[t]);
+}
+
 // adam_kernel's loop with the record read once per thread.  A skipped step reads p alone and
 // writes only the shadow.  decay_mask: one byte per 64 elements (16 consecutive 16-B groups).
 template <bool LP>
@@ -223,16 +236,7 @@ __global__ __launch_bounds__(256) void adam_ctl_kernel(int64_t n, float* __restr
   const bool tail = t < n && t < n4 * 4 + 4;
   const float coef = ctl ? ctl->coef : 1.f;
   if (ctl && ctl->skip) {
-    if constexpr (LP) {
-      for (int64_t i = first; i < n4; i += stride) {
-        const f32x4 pv = ld_s((const f32x4*)p + i);
-        bf16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = from_f32<bf16>(pv[e]);
-        ((bf16x4*)lp)[i] = o;
-      }
-      if (tail) lp[t] = from_f32<bf16>(p[t]);
-    }
+    if constexpr (LP) shadow_only(n4, first, stride, tail, t, p, lp);
     return;
   }
   constexpr int U = ADAM_U;
@@ -281,6 +285,119 @@ __global__ __launch_bounds__(256) void adam_ctl_kernel(int64_t n, float* __restr
     m[t] = me;
     v[t] = ve;
     if constexpr (LP) lp[t] = from_f32<bf16>(pe);
+  }
+}
+
+// ---------------------------------------------------------------- EMA of the weights
+// keras.optimizers.Adam(use_ema=True): e <- mom e + (1 - mom) p_new, three rounded fp32 ops on the
+// parameter the step has just produced (one_m = 1 - mom is formed on the host, in fp32).
+__device__ __forceinline__ float ema1(float e, float p, float mom, float one_m) {
+  return __fadd_rn(__fmul_rn(mom, e), __fmul_rn(one_m, p));
+}
+
+// adam_ctl_kernel's loop with the average as a fifth stream: 4 B read and 4 B written per parameter
+// on top of the step's.  A skipped step neither reads nor writes e.
+// Measured at the ViT-B arena (tools/ema_bench.py, two processes of three rounds each): 546-564 us as
+// written (ADAM_U = 2, streaming load of e), 580-588 us with a plain load of e, 600-604 us with one
+// 16-B group per thread in flight.
+template <bool LP>
+__global__ __launch_bounds__(256) void adam_ema_kernel(int64_t n, float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v,
+                                                       bf16* __restrict__ lp, AdamArgs a, float wd, float lr,
+                                                       const uint8_t* __restrict__ mask,
+                                                       const ClipCtl* __restrict__ ctl, float* __restrict__ ema,
+                                                       float mom, float one_m) {
+  const int64_t n4 = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t t = n4 * 4 + first;   // tail (n % 4) by the first threads
+  const bool tail = t < n && t < n4 * 4 + 4;
+  const float coef = ctl ? ctl->coef : 1.f;
+  if (ctl && ctl->skip) {
+    if constexpr (LP) shadow_only(n4, first, stride, tail, t, p, lp);
+    return;
+  }
+  constexpr int U = ADAM_U;
+  for (int64_t i0 = first; i0 < n4; i0 += U * stride) {
+    f32x4 pv[U], gv[U], mv[U], vv[U], ev[U];
+    bool dec[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      dec[u] = false;
+      if (u == 0 || i < n4) {
+        pv[u] = ld_s((const f32x4*)p + i);
+        gv[u] = ld_s((const f32x4*)g + i);
+        mv[u] = ld_s((const f32x4*)m + i);
+        vv[u] = ld_s((const f32x4*)v + i);
+        ev[u] = ld_s((const f32x4*)ema + i);
+        dec[u] = wd != 0.f && (!mask || mask[i >> 4] != 0);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      if (u > 0 && i >= n4) break;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pv[u][e], me = mv[u][e], ve = vv[u][e];
+        adam1_ctl(a, coef, dec[u], wd, lr, pe, gv[u][e], me, ve);
+        pv[u][e] = pe;
+        mv[u][e] = me;
+        vv[u][e] = ve;
+        ev[u][e] = ema1(ev[u][e], pe, mom, one_m);
+      }
+      st_s((f32x4*)p + i, pv[u]);
+      st_s((f32x4*)m + i, mv[u]);
+      st_s((f32x4*)v + i, vv[u]);
+      st_s((f32x4*)ema + i, ev[u]);
+      if constexpr (LP) {
+        bf16x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = from_f32<bf16>(pv[u][e]);
+        ((bf16x4*)lp)[i] = o;
+      }
+    }
+  }
+  if (tail) {
+    float pe = p[t], me = m[t], ve = v[t];
+    adam1_ctl(a, coef, wd != 0.f && (!mask || mask[t >> 6] != 0), wd, lr, pe, g[t], me, ve);
+    p[t] = pe;
+    m[t] = me;
+    v[t] = ve;
+    ema[t] = ema1(ema[t], pe, mom, one_m);
+    if constexpr (LP) lp[t] = from_f32<bf16>(pe);
+  }
+}
+
+// Using the average: SWAP exchanges p and ema in place (a thread loads both 16-B groups at its
+// index, then stores both: no temporary), otherwise p <- ema; the shadow of the new p rides along.
+template <bool LP, bool SWAP>
+__global__ __launch_bounds__(256) void ema_apply_kernel(int64_t n, float* __restrict__ p, float* __restrict__ ema,
+                                                        bf16* __restrict__ lp) {
+  const int64_t n4 = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (int64_t i = first; i < n4; i += stride) {
+    const f32x4 ev = ld_s((const f32x4*)ema + i);
+    if constexpr (SWAP) {
+      const f32x4 pv = ld_s((const f32x4*)p + i);
+      st_s((f32x4*)ema + i, pv);
+    }
+    st_s((f32x4*)p + i, ev);
+    if constexpr (LP) {
+      bf16x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = from_f32<bf16>(ev[e]);
+      ((bf16x4*)lp)[i] = o;
+    }
+  }
+  const int64_t t = n4 * 4 + first;   // tail (n % 4) by the first threads
+  if (t < n && t < n4 * 4 + 4) {
+    const float ee = ema[t];
+    if constexpr (SWAP) ema[t] = p[t];
+    p[t] = ee;
+    if constexpr (LP) lp[t] = from_f32<bf16>(ee);
   }
 }
 
@@ -360,5 +477,48 @@ extern "C" int vitmi_adam_step_ctl(int64_t n, float* p, const float* g, float* m
          0, (double)n * (p_lp ? 30 : 28) + extra, n, p, g, m, v, (bf16*)p_lp, a, weight_decay, lr, decay_mask,
          (const ClipCtl*)ctl);
   VITMI_LAUNCH_CHECK("adam_step_ctl");
+  return VITMI_OK;
+}
+
+extern "C" int vitmi_adam_step_ema(int64_t n, float* p, const float* g, float* m, float* v, void* p_lp, float alpha,
+                                   double beta_1, double beta_2, float epsilon, float grad_scale, float weight_decay,
+                                   float lr, const uint8_t* decay_mask, const void* ctl, float* ema,
+                                   float ema_momentum, vitmi_stream_t stream) {
+  VITMI_CHECK_ARG(n >= 0, "adam_step_ema: n < 0");
+  VITMI_CHECK_ARG(beta_1 >= 0.0 && beta_1 < 1.0 && beta_2 >= 0.0 && beta_2 < 1.0 && epsilon >= 0.f,
+                  "adam_step_ema: bad hyper-parameters");
+  VITMI_CHECK_ARG(weight_decay >= 0.f, "adam_step_ema: weight_decay must be >= 0");
+  VITMI_CHECK_ARG(ema_momentum >= 0.f && ema_momentum < 1.f, "adam_step_ema: ema_momentum must be in [0, 1)");
+  if (n == 0) return VITMI_OK;
+  VITMI_CHECK_ARG(p && g && m && v && ema, "adam_step_ema: null pointer");
+  VITMI_CHECK_ARG(aligned_to(p, 16) && aligned_to(g, 16) && aligned_to(m, 16) && aligned_to(v, 16) &&
+                      aligned_to(ema, 16),
+                  "adam_step_ema: fp32 buffers must be 16-byte aligned");
+  VITMI_CHECK_ARG(aligned_to(p_lp, 8), "adam_step_ema: bf16 shadow must be 8-byte aligned");
+  VITMI_CHECK_ARG(aligned_to(ctl, 16), "adam_step_ema: the clip record must be 16-byte aligned");
+  AdamArgs a{alpha, (float)(1.0 - beta_1), (float)(1.0 - beta_2), epsilon, grad_scale};
+  // as adam_step_ctl, plus the average read and written
+  const double extra = (decay_mask && weight_decay != 0.f ? (double)((n + 63) / 64) : 0.0) + (ctl ? 16.0 : 0.0);
+  launch(p_lp ? adam_ema_kernel<true> : adam_ema_kernel<false>, dim3(grid_cap(n / 4)), dim3(256), (hipStream_t)stream,
+         0, (double)n * (p_lp ? 38 : 36) + extra, n, p, g, m, v, (bf16*)p_lp, a, weight_decay, lr, decay_mask,
+         (const ClipCtl*)ctl, ema, ema_momentum, 1.f - ema_momentum);
+  VITMI_LAUNCH_CHECK("adam_step_ema");
+  return VITMI_OK;
+}
+
+extern "C" int vitmi_ema_apply(int64_t n, float* p, float* ema, void* p_lp, int mode, vitmi_stream_t stream) {
+  VITMI_CHECK_ARG(n >= 0, "ema_apply: n < 0");
+  VITMI_CHECK_ARG(mode == 0 || mode == 1, "ema_apply: mode must be 0 (swap) or 1 (copy)");
+  if (n == 0) return VITMI_OK;
+  VITMI_CHECK_ARG(p && ema, "ema_apply: null pointer");
+  VITMI_CHECK_ARG(aligned_to(p, 16) && aligned_to(ema, 16), "ema_apply: fp32 buffers must be 16-byte aligned");
+  VITMI_CHECK_ARG(aligned_to(p_lp, 8), "ema_apply: bf16 shadow must be 8-byte aligned");
+  const bool swap = mode == 0;
+  auto kernel = p_lp ? (swap ? ema_apply_kernel<true, true> : ema_apply_kernel<true, false>)
+                     : (swap ? ema_apply_kernel<false, true> : ema_apply_kernel<false, false>);
+  // swap: p and ema read and written; copy: ema read, p written (+ the bf16 shadow)
+  launch(kernel, dim3(grid_cap(n / 4)), dim3(256), (hipStream_t)stream, 0,
+         (double)n * ((swap ? 16 : 8) + (p_lp ? 2 : 0)), n, p, ema, (bf16*)p_lp);
+  VITMI_LAUNCH_CHECK("ema_apply");
   return VITMI_OK;
 }

@@ -95,6 +95,8 @@ SIGNATURES = {
     "vitmi_grad_sumsq": (I, [L, P, P, P]),
     "vitmi_clip_finalize": (I, [L, P, F, F, I, P, P]),
     "vitmi_adam_step_ctl": (I, [L, P, P, P, P, P, F, D, D, F, F, F, F, P, P, P]),
+    "vitmi_adam_step_ema": (I, [L, P, P, P, P, P, F, D, D, F, F, F, F, P, P, P, F, P]),
+    "vitmi_ema_apply": (I, [L, P, P, P, I, P]),
     "vitmi_softmax_xent_workspace_size": (S, [I]),
     "vitmi_softmax_xent": (I, [I, I, P, L, P, P, P, P, L, F, I, P, P, P, L, P, P, S, P]),
     "vitmi_mix_batch": (I, [I, I, I, I, P, P, P, P, P, P]),

@@ -4,7 +4,8 @@
 
 One safetensors file (no pickling; h5py is not in this image): every parameter and buffer
 (BatchNorm moving statistics included) under its module path, plus optionally the optimizer's
-moments and step count under ``optimizer/...``.  Loading checks names and shapes strictly.
+moments and step count (and its average of the weights, ``use_ema``) under ``optimizer/...``.
+Loading checks names and shapes strictly.
 """
 from __future__ import annotations
 
@@ -36,6 +37,12 @@ def save_weights(model, path: str, optimizer=None, metadata: Optional[Dict[str, 
         else:
             t["optimizer/m"] = sd["m"].contiguous().cpu()
             t["optimizer/v"] = sd["v"].contiguous().cpu()
+        ema = sd.get("ema")
+        if isinstance(ema, list):
+            for i, e in enumerate(ema):
+                t[f"optimizer/ema/{i}"] = e.contiguous().cpu()
+        elif ema is not None:
+            t["optimizer/ema"] = ema.contiguous().cpu()
     save_file(t, path, metadata=meta)
 
 
@@ -66,5 +73,11 @@ def load_weights(model, path: str, optimizer=None, strict: bool = True) -> None:
             n = sum(1 for k in t if k.startswith("optimizer/m/"))
             m = [t[f"optimizer/m/{i}"] for i in range(n)]
             v = [t[f"optimizer/v/{i}"] for i in range(n)]
-        optimizer.load_state_dict({"iterations": int(meta["optimizer.iterations"]),
-                                   "learning_rate": float(meta["optimizer.learning_rate"]), "m": m, "v": v})
+        sd = {"iterations": int(meta["optimizer.iterations"]),
+              "learning_rate": float(meta["optimizer.learning_rate"]), "m": m, "v": v}
+        # files written without an average hold neither key: the optimizer then starts its own
+        if "optimizer/ema" in t:
+            sd["ema"] = t["optimizer/ema"]
+        elif "optimizer/ema/0" in t:
+            sd["ema"] = [t[f"optimizer/ema/{i}"] for i in range(sum(1 for k in t if k.startswith("optimizer/ema/")))]
+        optimizer.load_state_dict(sd)

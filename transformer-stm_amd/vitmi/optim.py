@@ -12,10 +12,16 @@ one launch per parameter tensor.
 the device: a fixed-order fp64 sum of squares of the gradients (``vitmi_grad_sumsq``), one
 finalize launch that writes a 16-byte record (``vitmi_clip_finalize``), and the step reading it
 (``vitmi_adam_step_ctl``).  No host read, no torch reduction kernel.
+
+``use_ema`` keeps Keras' exponential moving average of the weights inside the same launch
+(``vitmi_adam_step_ema``: the updated parameter is in a register, the average costs one 4-byte
+read and one 4-byte write per parameter) and ``vitmi_ema_apply`` exchanges or copies it into the
+parameters, bf16 shadow included, for evaluation.
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, List, Optional, Tuple
+import contextlib
+from typing import Callable, Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -34,9 +40,22 @@ def keras_alpha(lr: float, beta_1: float, beta_2: float, step: int) -> float:
     return float(f(lr) * np.sqrt(f(1) - b2p, dtype=np.float32) / (f(1) - b1p))
 
 
+def ema_momentum_at(t: int, ema_momentum: Union[float, Callable[[int], float]]) -> float:
+    """The momentum of the weight average at step ``t`` (1-based, ``Adam.iterations``): 0 at the
+    first step (Keras' ``not_first_step``: the first average is the first updated weights),
+    otherwise the value, or ``ema_momentum(t)`` for a callable, rounded once to float32.
+    ``ValueError`` unless the rounded value is in [0, 1)."""
+    x = ema_momentum(t) if callable(ema_momentum) else ema_momentum
+    x = float(np.float32(x))
+    if not 0.0 <= x < 1.0:
+        raise ValueError(f"vitmi Adam: ema_momentum must be in [0, 1) as float32, got {x!r} at step {t}")
+    return 0.0 if t == 1 else x
+
+
 class Adam:
     """keras.optimizers.Adam(learning_rate, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
-    global_clipnorm=None, weight_decay=None).
+    global_clipnorm=None, weight_decay=None, use_ema=False, ema_momentum=0.99,
+    ema_overwrite_frequency=None).
 
     ``target``: a model with ``arena()`` (VisionTransformer: single fused launch + bf16 shadow
     refresh) or an iterable of parameters.  ``grad_scale`` multiplies the gradients as they are
@@ -58,12 +77,30 @@ class Adam:
     ``step()`` calls, and ``alpha`` follows ``iterations``: after a skipped step the bias
     correction runs slightly ahead of the moments, which errs towards a smaller step and vanishes
     as ``t`` grows.  ``skipped_steps`` reads the device counter (the only accessor that
-    synchronises); ``last_clip()`` returns the last step's ``(norm, coef)`` as device tensors."""
+    synchronises); ``last_clip()`` returns the last step's ``(norm, coef)`` as device tensors.
+
+    ``use_ema``: an fp32 average of the parameters, ``e = momentum * e + (1 - momentum) * p`` after
+    every update, three rounded fp32 operations inside the step's own launch.  It starts as a copy of
+    the parameters; the momentum of step ``t`` is ``ema_momentum_at(t, ema_momentum)`` (a float in
+    [0, 1) or a host callable ``t -> float``, e.g. a warm-up).  Parameters that are not stepped
+    (frozen, or without a gradient) keep their average as it is, and so does every parameter across a
+    step skipped by ``skip_nonfinite``.  ``ema_overwrite_frequency=k`` copies the average into the
+    stepped parameters after every k-th step; ``finalize_variable_values()`` does so for all of them
+    (``train.fit`` calls it after the last epoch, Keras' ``on_train_end``).  ``swap_ema()`` exchanges
+    parameters and average in place and ``with opt.ema_weights():`` does so around a block (an
+    evaluation), swapping back even when the block raises; inside the block ``step()``,
+    ``state_dict()``, ``load_state_dict()``, ``swap_ema()`` and a nested ``ema_weights()`` raise.
+    Only parameters are averaged and swapped: buffers such as BatchNorm moving statistics are not.
+    ``state_dict()`` carries the average as ``"ema"``; a state without it loaded into a
+    ``use_ema`` optimizer resets the average to the current parameters, so load the weights first,
+    then the optimizer state."""
 
     def __init__(self, target, learning_rate: float = 1e-3, beta_1: float = 0.9, beta_2: float = 0.999,
                  epsilon: float = 1e-7, grad_scale: float = 1.0, global_clipnorm: Optional[float] = None,
                  weight_decay: float = 0.0, decay_filter: Optional[Callable[[str, Tensor], bool]] = None,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, use_ema: bool = False,
+                 ema_momentum: Union[float, Callable[[int], float]] = 0.99,
+                 ema_overwrite_frequency: Optional[int] = None):
         self.learning_rate = float(learning_rate)
         self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
         self.grad_scale = float(grad_scale)
@@ -74,6 +111,15 @@ class Adam:
         self.global_clipnorm = None if global_clipnorm is None else float(global_clipnorm)
         self.weight_decay = float(weight_decay)
         self.skip_nonfinite = bool(skip_nonfinite)
+        self.use_ema = bool(use_ema)
+        if not callable(ema_momentum):
+            ema_momentum_at(2, ema_momentum)        # validates
+        self.ema_momentum = ema_momentum
+        if ema_overwrite_frequency is not None:
+            if isinstance(ema_overwrite_frequency, bool) or not isinstance(ema_overwrite_frequency, int) \
+                    or ema_overwrite_frequency < 1:
+                raise ValueError("vitmi Adam: ema_overwrite_frequency must be an int >= 1 (None = never)")
+        self.ema_overwrite_frequency = ema_overwrite_frequency
         self.iterations = 0
         self._model = target if hasattr(target, "arena") else None
         if self._model is not None:
@@ -94,6 +140,11 @@ class Adam:
             self._decays = [bool(decay_filter(names.get(id(p), ""), p)) for p in self.params]
         else:
             self._decays = [p.ndim >= 2 and id(p) not in no_decay for p in self.params]
+        # the average: a flat fp32 buffer at the arena's offsets, or one tensor per parameter
+        self._ema = None
+        if self.use_ema:
+            self._ema = arena.flat.clone() if self._arena is not None else [p.detach().clone() for p in self.params]
+        self._in_ema_weights = False
         self._mask: Optional[Tensor] = None       # arena: one byte per 64 elements, built once
         self._ctl: Optional[Tensor] = None        # the 16-byte device record (coef, norm, skip, skipped_total)
         self._partials: Optional[Tensor] = None   # fp64 chunk sums of every stepped run / tensor
@@ -116,7 +167,7 @@ class Adam:
         if red.flat.data_ptr() != self._arena.grad.data_ptr() or red.flat.numel() != self._arena.grad.numel():
             raise ValueError("vitmi Adam.overlap_with: the reducer is not over this model's gradient arena")
         self._ov = {"stream": torch.cuda.Stream(device=self._arena.flat.device), "done": 0, "alpha": None,
-                    "lr": None, "skip": False}
+                    "lr": None, "mom": None, "skip": False}
         red.listeners.append(self._on_bucket)
 
     # -- clipping / decay / skipping state
@@ -170,9 +221,9 @@ class Adam:
         return ctl[1], ctl[0]
 
     def _launch(self, s0: int, e0: int, alpha: float, lr: Optional[float] = None,
-                ctl: Optional[Tensor] = None) -> None:
+                ctl: Optional[Tensor] = None, mom: Optional[float] = None) -> None:
         arena, lp = self._arena, self._arena.flat_lp
-        if ctl is None and self.weight_decay == 0.0:
+        if self._ema is None and ctl is None and self.weight_decay == 0.0:
             check(lib().vitmi_adam_step(e0 - s0, ops._p(arena.flat[s0:]), ops._p(arena.grad[s0:]),
                                         ops._p(self._m[s0:]), ops._p(self._v[s0:]),
                                         ops._p(lp[s0:]) if lp is not None else None, alpha,
@@ -184,6 +235,15 @@ class Adam:
             if s0 % arena.ALIGN:
                 raise RuntimeError("vitmi Adam: weight decay needs step ranges on 64-element boundaries")
             mask = ops._p(self._decay_mask()[s0 // arena.ALIGN:])
+        if self._ema is not None:
+            check(lib().vitmi_adam_step_ema(e0 - s0, ops._p(arena.flat[s0:]), ops._p(arena.grad[s0:]),
+                                            ops._p(self._m[s0:]), ops._p(self._v[s0:]),
+                                            ops._p(lp[s0:]) if lp is not None else None, alpha,
+                                            self.beta_1, self.beta_2, self.epsilon, self.grad_scale,
+                                            self.weight_decay, self.learning_rate if lr is None else lr, mask,
+                                            ops._p(ctl), ops._p(self._ema[s0:]), mom, ops._s()),
+                  "adam_step_ema")
+            return
         check(lib().vitmi_adam_step_ctl(e0 - s0, ops._p(arena.flat[s0:]), ops._p(arena.grad[s0:]),
                                         ops._p(self._m[s0:]), ops._p(self._v[s0:]),
                                         ops._p(lp[s0:]) if lp is not None else None, alpha,
@@ -203,6 +263,8 @@ class Adam:
                 return
             ov["alpha"] = keras_alpha(self.learning_rate, self.beta_1, self.beta_2, self.iterations + 1)
             ov["lr"] = self.learning_rate
+            if self._ema is not None:
+                ov["mom"] = ema_momentum_at(self.iterations + 1, self.ema_momentum)
         if s0 != ov["done"]:
             raise RuntimeError("vitmi Adam: gradient buckets finished out of order")
         side = ov["stream"]
@@ -210,7 +272,7 @@ class Adam:
         ready.record(stream if stream is not None else torch.cuda.current_stream(self._arena.flat.device))
         side.wait_event(ready)
         with torch.cuda.stream(side):
-            self._launch(s0, e0, ov["alpha"], ov["lr"])
+            self._launch(s0, e0, ov["alpha"], ov["lr"], None, ov["mom"])
         ov["done"] = e0
 
     # -- keras-style schedule hook
@@ -235,8 +297,13 @@ class Adam:
 
     @torch.no_grad()
     def step(self) -> None:
+        self._not_in_ema_weights("step")
+        # (a callable momentum out of range raises here, before the step is counted)
+        mom = ema_momentum_at(self.iterations + 1, self.ema_momentum) if self._ema is not None else None
         self.iterations += 1
         alpha = keras_alpha(self.learning_rate, self.beta_1, self.beta_2, self.iterations)
+        k = self.ema_overwrite_frequency
+        overwrite = self._ema is not None and k is not None and self.iterations % k == 0
         if self._arena is not None:
             arena = self._model.arena()
             if arena is not self._arena:
@@ -251,23 +318,26 @@ class Adam:
             if ov is not None:
                 if self._use_ctl():
                     raise ValueError("vitmi Adam: global_clipnorm / skip_nonfinite cannot be used with overlap_with")
-                done, ov_alpha, ov_lr = ov["done"], ov["alpha"], ov["lr"]
-                ov["done"], ov["alpha"], ov["lr"], ov["skip"] = 0, None, None, False
+                done, ov_alpha, ov_lr, ov_mom = ov["done"], ov["alpha"], ov["lr"], ov["mom"]
+                ov["done"], ov["alpha"], ov["lr"], ov["mom"], ov["skip"] = 0, None, None, None, False
                 if done:
                     # the buckets the backward finished were stepped on the side stream
                     torch.cuda.current_stream(arena.flat.device).wait_stream(ov["stream"])
-                    alpha, lr = ov_alpha, ov_lr
+                    alpha, lr, mom = ov_alpha, ov_lr, ov_mom
             if not any(stepping):
                 return
             lp = arena.flat_lp
             if not all(stepping):
                 arena.refresh_lp()          # the skipped parameters' shadow must be current too
             arena.bind_grads(fill_missing=all(stepping))
-            runs = [(max(s0, done), e0) for s0, e0 in arena.runs(stepping) if e0 > max(s0, done)]
+            stepped = arena.runs(stepping)
+            runs = [(max(s0, done), e0) for s0, e0 in stepped if e0 > max(s0, done)]
             # the norm is over the gradients of the parameters being stepped, and only those
             ctl = self._clip([(arena.grad[s0:], e0 - s0) for s0, e0 in runs]) if self._use_ctl() else None
             for s0, e0 in runs:
-                self._launch(s0, e0, alpha, lr, ctl)
+                self._launch(s0, e0, alpha, lr, ctl, mom)
+            if overwrite:
+                self._ema_apply(1, stepped)
             arena.mark_lp_fresh()
             return
         todo = [(p, m, v, dec) for p, m, v, dec in zip(self.params, self._m, self._v, self._decays)
@@ -278,8 +348,17 @@ class Adam:
         if not todo:
             return
         ctl = self._clip([(p.grad, p.numel()) for p, _, _, _ in todo]) if self._use_ctl() else None
+        emas = {id(p): e for p, e in zip(self.params, self._ema)} if self._ema is not None else {}
         for p, m, v, dec in todo:
-            if ctl is None and self.weight_decay == 0.0:
+            if self._ema is not None:
+                check(lib().vitmi_adam_step_ema(p.numel(), ops._p(p), ops._p(p.grad), ops._p(m), ops._p(v), None,
+                                                alpha, self.beta_1, self.beta_2, self.epsilon, self.grad_scale,
+                                                self.weight_decay if dec else 0.0, self.learning_rate, None,
+                                                ops._p(ctl), ops._p(emas[id(p)]), mom, ops._s()), "adam_step_ema")
+                if overwrite:
+                    check(lib().vitmi_ema_apply(p.numel(), ops._p(p), ops._p(emas[id(p)]), None, 1, ops._s()),
+                          "ema_apply")
+            elif ctl is None and self.weight_decay == 0.0:
                 check(lib().vitmi_adam_step(p.numel(), ops._p(p), ops._p(p.grad), ops._p(m), ops._p(v), None, alpha,
                                             self.beta_1, self.beta_2, self.epsilon, self.grad_scale, ops._s()),
                       "adam_step")
@@ -293,15 +372,103 @@ class Adam:
             # that owns p (its bf16 operand shadow is keyed on these counters) re-casts it
             torch.autograd.graph.increment_version(p)
 
+    # -- the average of the weights
+    def _need_ema(self, what: str) -> None:
+        if self._ema is None:
+            raise RuntimeError(f"vitmi Adam.{what}: the optimizer was created with use_ema=False")
+
+    def _not_in_ema_weights(self, what: str) -> None:
+        if self._in_ema_weights:
+            raise RuntimeError(f"vitmi Adam.{what}: not inside ema_weights(): the parameters hold the average")
+
+    def _ema_apply(self, mode: int, ranges: Optional[List[Tuple[int, int]]] = None) -> None:
+        """vitmi_ema_apply (0: exchange, 1: p <- ema) over arena ranges (default: the whole arena),
+        shadow included, or over every tensor of a parameter list."""
+        if self._arena is not None:
+            arena, lp = self._arena, self._arena.flat_lp
+            if self._model.arena() is not arena:
+                raise RuntimeError("vitmi Adam: the model's parameter arena was rebuilt after the optimizer "
+                                   "was created (model moved?); create the optimizer after placing the model")
+            for s0, e0 in ([(0, arena.numel)] if ranges is None else ranges):
+                check(lib().vitmi_ema_apply(e0 - s0, ops._p(arena.flat[s0:]), ops._p(self._ema[s0:]),
+                                            ops._p(lp[s0:]) if lp is not None else None, mode, ops._s()),
+                      "ema_apply")
+            if ranges is None:
+                arena.mark_lp_fresh()
+            return
+        for p, e in zip(self.params, self._ema):
+            if not p.is_contiguous():
+                raise RuntimeError("vitmi Adam: parameters must be contiguous")
+            check(lib().vitmi_ema_apply(p.numel(), ops._p(p), ops._p(e), None, mode, ops._s()), "ema_apply")
+            torch.autograd.graph.increment_version(p)
+
+    @torch.no_grad()
+    def swap_ema(self) -> None:
+        """Exchange parameters and average in place (one launch over the arena, bf16 shadow
+        included; one per tensor for a parameter list).  Twice restores both."""
+        self._need_ema("swap_ema")
+        self._not_in_ema_weights("swap_ema")
+        self._ema_apply(0)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with opt.ema_weights():`` the model computes with the averaged weights; the training
+        weights come back on leaving, also when the block raises."""
+        self._need_ema("ema_weights")
+        self._not_in_ema_weights("ema_weights")
+        with torch.no_grad():
+            self._ema_apply(0)
+        self._in_ema_weights = True
+        try:
+            yield self
+        finally:
+            self._in_ema_weights = False
+            with torch.no_grad():
+                self._ema_apply(0)
+
+    @torch.no_grad()
+    def finalize_variable_values(self) -> None:
+        """Keras' name: every parameter becomes its average (the average stays)."""
+        self._need_ema("finalize_variable_values")
+        self._not_in_ema_weights("finalize_variable_values")
+        self._ema_apply(1)
+
+    @torch.no_grad()
+    def reset_ema(self) -> None:
+        """The average becomes a copy of the current parameters."""
+        self._need_ema("reset_ema")
+        self._not_in_ema_weights("reset_ema")
+        if self._arena is not None:
+            self._ema.copy_(self._arena.flat)
+        else:
+            for e, p in zip(self._ema, self.params):
+                e.copy_(p.detach())
+
+    def ema_parameters(self):
+        """The average, as views: ``{name: tensor}`` for an arena model, a list aligned with
+        ``params`` for a parameter list."""
+        self._need_ema("ema_parameters")
+        if self._arena is not None:
+            return {k: self._arena.view(self._ema, p) for k, p in self._model.named_parameters()}
+        return list(self._ema)
+
     # -- checkpointing (Keras saves the optimizer variables with the model weights)
     def state_dict(self) -> Dict:
+        self._not_in_ema_weights("state_dict")
         if self._arena is not None:
-            return {"iterations": self.iterations, "learning_rate": self.learning_rate, "m": self._m.clone(),
-                    "v": self._v.clone()}
-        return {"iterations": self.iterations, "learning_rate": self.learning_rate,
-                "m": [t.clone() for t in self._m], "v": [t.clone() for t in self._v]}
+            sd = {"iterations": self.iterations, "learning_rate": self.learning_rate, "m": self._m.clone(),
+                  "v": self._v.clone()}
+            if self._ema is not None:
+                sd["ema"] = self._ema.clone()
+            return sd
+        sd = {"iterations": self.iterations, "learning_rate": self.learning_rate,
+              "m": [t.clone() for t in self._m], "v": [t.clone() for t in self._v]}
+        if self._ema is not None:
+            sd["ema"] = [t.clone() for t in self._ema]
+        return sd
 
     def load_state_dict(self, sd: Dict) -> None:
+        self._not_in_ema_weights("load_state_dict")
         self.iterations = int(sd["iterations"])
         self.learning_rate = float(sd["learning_rate"])
         with torch.no_grad():
@@ -313,6 +480,14 @@ class Adam:
                     dst.copy_(src)
                 for dst, src in zip(self._v, sd["v"]):
                     dst.copy_(src)
+            if self._ema is not None:
+                if sd.get("ema") is None:
+                    self.reset_ema()
+                elif self._arena is not None:
+                    self._ema.copy_(sd["ema"])
+                else:
+                    for dst, src in zip(self._ema, sd["ema"]):
+                        dst.copy_(src)
 
 
 def keras_step_decay(epoch: int, lr: float, every: int = 50, factor: float = 0.8) -> float:
@@ -322,5 +497,5 @@ def keras_step_decay(epoch: int, lr: float, every: int = 50, factor: float = 0.8
     return lr
 
 
-__all__ = ["Adam", "keras_alpha", "keras_step_decay"]
+__all__ = ["Adam", "ema_momentum_at", "keras_alpha", "keras_step_decay"]
 

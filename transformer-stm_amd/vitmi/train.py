@@ -134,6 +134,8 @@ def fit(model, ds: SLSDataset, epochs: int, batch_size: int = 128, optimizer: Op
         hist["seconds"].append(time.perf_counter() - t0)
         if log is not None:
             log(" ".join(f"{k}={hist[k][-1]:.6g}" for k in hist if hist[k]))
+    if getattr(opt, "use_ema", False):
+        opt.finalize_variable_values()      # Keras' on_train_end: the model leaves with the averaged weights
     return hist
 
 
