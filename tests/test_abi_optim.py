@@ -1,5 +1,6 @@
 """CPU-side checks of the clipping / weight-decay entry points of the optimizer
-(include/vitmi.h: vitmi_grad_sumsq, vitmi_clip_finalize, vitmi_adam_step_ctl): host validation
+(include/vitmi.h: vitmi_grad_sumsq, vitmi_clip_finalize, vitmi_adam_step_ctl) and of the plain
+vitmi_adam_step, which shares its validation with the other two step entry points: host validation
 rejects bad arguments before any launch, and the partials count is ceil(n / CHUNK)."""
 import os
 import re
@@ -72,3 +73,59 @@ def test_adam_step_ctl_rejects_bad_arguments():
     rejected(call(wd=float("nan")), b"weight_decay")
     rejected(call(n=-1), b"n < 0")
     assert call(n=0) == 0                      # nothing to do
+
+
+BAD_HYPER = (dict(b1=1.0), dict(b1=-0.1), dict(b2=1.0), dict(b2=float("nan")), dict(eps=-1e-7))
+
+
+def test_adam_step_rejects_bad_arguments():
+    lib = _lib.lib()
+
+    def call(p=OK_PTR, g=OK_PTR, m=OK_PTR, v=OK_PTR, lp=None, n=100, b1=0.9, b2=0.999, eps=1e-7):
+        return lib.vitmi_adam_step(n, p, g, m, v, lp, 1e-3, b1, b2, eps, 1.0, None)
+
+    def refused(rc, word):
+        rejected(rc, word)
+        assert lib.vitmi_last_error().startswith(b"adam_step: ")      # its own name, not a sibling's
+
+    for name in ("p", "g", "m", "v"):
+        refused(call(**{name: None}), b"null")
+        refused(call(**{name: OK_PTR + 8}), b"16-byte")
+    refused(call(lp=OK_PTR + 2), b"8-byte")
+    refused(call(n=-1), b"n < 0")
+    for kw in BAD_HYPER:
+        refused(call(**kw), b"hyper-parameters")
+    assert call(n=0) == 0                      # nothing to do
+
+
+def test_adam_steps_judge_values_before_an_empty_range_and_pointers_after():
+    """All three step entry points alike: n == 0 with a bad value argument is refused, under the
+    entry point's own name; n == 0 with null pointers is OK."""
+    lib = _lib.lib()
+    hyper = dict(b1=0.9, b2=0.999, eps=1e-7)
+
+    def plain(n, ptr, wd=0.0, mom=0.5, **kw):
+        h = {**hyper, **kw}
+        return lib.vitmi_adam_step(n, ptr, ptr, ptr, ptr, None, 1e-3, h["b1"], h["b2"], h["eps"], 1.0, None)
+
+    def ctl(n, ptr, wd=0.0, mom=0.5, **kw):
+        h = {**hyper, **kw}
+        return lib.vitmi_adam_step_ctl(n, ptr, ptr, ptr, ptr, None, 1e-3, h["b1"], h["b2"], h["eps"], 1.0, wd, 1e-3,
+                                       None, None, None)
+
+    def ema(n, ptr, wd=0.0, mom=0.5, **kw):
+        h = {**hyper, **kw}
+        return lib.vitmi_adam_step_ema(n, ptr, ptr, ptr, ptr, None, 1e-3, h["b1"], h["b2"], h["eps"], 1.0, wd, 1e-3,
+                                       None, None, ptr, mom, None)
+
+    for name, call in (("adam_step", plain), ("adam_step_ctl", ctl), ("adam_step_ema", ema)):
+        for kw in BAD_HYPER:
+            rejected(call(0, OK_PTR, **kw), b"hyper-parameters")
+            assert lib.vitmi_last_error().startswith(name.encode() + b": ")
+        assert call(0, None) == 0
+        assert call(0, OK_PTR + 8) == 0        # nor is alignment judged for an empty range
+    for name, call in (("adam_step_ctl", ctl), ("adam_step_ema", ema)):
+        rejected(call(0, OK_PTR, wd=-0.1), b"weight_decay")
+        assert lib.vitmi_last_error().startswith(name.encode() + b": ")
+    rejected(ema(0, OK_PTR, mom=1.0), b"ema_momentum")
+    assert lib.vitmi_last_error().startswith(b"adam_step_ema: ")

@@ -242,7 +242,7 @@ def test_launch_records(shadow):
             _lib.check(_lib.lib().vitmi_adam_step_ema(n, P(p), P(g), P(m), P(v), P(lp), 1e-3, 0.9, 0.999, 1e-7, 1.0, wd,
                                                       LR, P(mk), P(ct), P(e), 0.99, _stream()), "adam_step_ema")
         torch.cuda.synchronize()
-        assert_recorded(st, kname("adam_ema_kernel", shadow), (1, 0.0, float(n * per + extra)),
+        assert_recorded(st, kname("adam_kernel", shadow, True, True), (1, 0.0, float(n * per + extra)),
                         f"adam ema shadow {shadow} extra {extra}")
     # swap: p and ema read and written; copy: ema read, p written
     for mode, by in ((0, 16), (1, 8)):

@@ -216,7 +216,9 @@ def test_adam_steps(lp):
               "adam_step")
     torch.cuda.synchronize()
     # p, g, m, v read; p, m, v (+ the bf16 shadow) written
-    assert_recorded(st, {kname("adam_kernel", lp): (1, 0.0, float(n * (30 if lp else 28)))}, f"adam lp {lp}")
+    # adam_kernel<LP, CTL, EMA>: each entry point records its own instance
+    assert_recorded(st, {kname("adam_kernel", lp, False, False): (1, 0.0, float(n * (30 if lp else 28)))},
+                    f"adam lp {lp}")
     ctl = torch.zeros(4, device=DEV)
     check(lib().vitmi_clip_finalize(0, None, 1.0, 0.0, 0, p(ctl), s()), "clip_finalize")
     with kernel_stats() as st:
@@ -224,8 +226,15 @@ def test_adam_steps(lp):
                                         None, p(ctl), s()), "adam_step_ctl")
     torch.cuda.synchronize()
     # as adam_step, plus the 16-byte clip record (no decay mask)
-    assert_recorded(st, {kname("adam_ctl_kernel", lp): (1, 0.0, float(n * (30 if lp else 28) + 16))},
+    assert_recorded(st, {kname("adam_kernel", lp, True, False): (1, 0.0, float(n * (30 if lp else 28) + 16))},
                     f"adam ctl lp {lp}")
+    # and the ctl instance it stays with no record and no decay: the argument values select nothing
+    with kernel_stats() as st:
+        check(lib().vitmi_adam_step_ctl(n, p(prm), p(g), p(m), p(v), p(shadow), 1e-3, 0.9, 0.999, 1e-7, 1.0, 0.0, 1e-3,
+                                        None, None, s()), "adam_step_ctl")
+    torch.cuda.synchronize()
+    assert_recorded(st, {kname("adam_kernel", lp, True, False): (1, 0.0, float(n * (30 if lp else 28)))},
+                    f"adam ctl, no record, lp {lp}")
 
 
 # ---------------------------------------------------------------- split.hip

@@ -157,27 +157,58 @@ def test_adam_step_ctl_clipped_bit_exact(n, scale):
     assert opt.skipped_steps == 0
 
 
-@pytest.mark.parametrize("n", [1, 7, 1_000_003])
+# under the 8192-block grid cap (2 097 152 threads, two 16-B groups each): a thread's second group is
+# partly in range at the first size, and the grid-stride loop takes a second trip at the second
+BIG_PARTIAL, BIG_SECOND_TRIP = 8_388_608 + 1031, 16_777_216 + 1203
+PAD, SENTINEL = 64, -77.0          # the sentinel is exact in bf16 too
+
+
+def guarded(n, init=None, dtype=torch.float32):
+    """-> (n elements PAD elements into an allocation whose margins hold the sentinel, the allocation)"""
+    full = torch.full((n + 2 * PAD,), SENTINEL, dtype=dtype, device=DEV)
+    inner = full[PAD:PAD + n]
+    inner.copy_(init) if init is not None else inner.zero_()
+    return inner, full
+
+
+def margins_intact(full):
+    return bool((full[:PAD] == SENTINEL).all()) and bool((full[-PAD:] == SENTINEL).all())
+
+
+def int_bits(t):
+    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+
+
+@pytest.mark.parametrize("n", [1, 7, 1_000_003, BIG_PARTIAL, BIG_SECOND_TRIP])
 def test_adam_step_ctl_without_record_equals_adam_step(n):
     lib = _lib.lib()
-    g = torch.Generator().manual_seed(n + 1)
-    p0 = torch.randn(n, generator=g)
-    state = []
-    for _ in range(2):
-        state.append([p0.to(DEV), torch.zeros(n, device=DEV), torch.zeros(n, device=DEV),
-                      torch.zeros(n, dtype=torch.bfloat16, device=DEV)])
-    for t in range(1, 4):
-        gd = (torch.randn(n, generator=g) * (10.0 ** (t - 2))).to(DEV)
-        alpha = optim.keras_alpha(1e-3, 0.9, 0.999, t)
-        (p, m, v, lp), (q, mq, vq, lq) = state
-        _lib.check(lib.vitmi_adam_step(n, p.data_ptr(), gd.data_ptr(), m.data_ptr(), v.data_ptr(), lp.data_ptr(),
-                                       alpha, 0.9, 0.999, 1e-7, 0.5, _stream()), "adam_step")
-        _lib.check(lib.vitmi_adam_step_ctl(n, q.data_ptr(), gd.data_ptr(), mq.data_ptr(), vq.data_ptr(),
-                                           lq.data_ptr(), alpha, 0.9, 0.999, 1e-7, 0.5, 0.0, 1e-3, None, None,
-                                           _stream()), "adam_step_ctl")
-        torch.cuda.synchronize()
-        for a, b in zip(*state):
-            assert torch.equal(a, b), t
+    ptr = lambda t: t.data_ptr() if t is not None else None    # noqa: E731
+    for shadow in (True, False):
+        g = torch.Generator().manual_seed(n + 1)
+        p0 = torch.randn(n, generator=g)
+        state = []
+        for _ in range(2):
+            state.append([guarded(n, p0), guarded(n), guarded(n),
+                          guarded(n, dtype=torch.bfloat16) if shadow else (None, None)])
+        for t in range(1, 4):
+            gd, g_full = guarded(n, torch.randn(n, generator=g) * (10.0 ** (t - 2)))
+            g_before = gd.clone()
+            alpha = optim.keras_alpha(1e-3, 0.9, 0.999, t)
+            (p, m, v, lp), (q, mq, vq, lq) = ([x[0] for x in s] for s in state)
+            _lib.check(lib.vitmi_adam_step(n, ptr(p), ptr(gd), ptr(m), ptr(v), ptr(lp), alpha, 0.9, 0.999, 1e-7, 0.5,
+                                           _stream()), "adam_step")
+            _lib.check(lib.vitmi_adam_step_ctl(n, ptr(q), ptr(gd), ptr(mq), ptr(vq), ptr(lq), alpha, 0.9, 0.999, 1e-7,
+                                               0.5, 0.0, 1e-3, None, None, _stream()), "adam_step_ctl")
+            torch.cuda.synchronize()
+            for (a, a_full), (b, b_full) in zip(*state):
+                if a is None:
+                    continue
+                assert torch.equal(int_bits(a), int_bits(b)), (t, shadow)
+                assert margins_intact(a_full) and margins_intact(b_full), (t, shadow)
+            assert torch.equal(int_bits(gd), int_bits(g_before)) and margins_intact(g_full)    # only read
+            if shadow:
+                assert torch.equal(int_bits(lp), int_bits(p.to(torch.bfloat16))), t
+        assert not torch.equal(state[0][0][0], p0.to(DEV))             # the steps really moved the parameters
 
 
 def _decayed(p, wd, lr, sel):

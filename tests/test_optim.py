@@ -41,6 +41,57 @@ def test_adam_per_tensor_bit_exact(n, scale):
         assert np.array_equal(opt._v[0].cpu().numpy(), ref[2])
 
 
+# under the 8192-block grid cap (2 097 152 threads, two 16-B groups each): a thread's second group is
+# partly in range at the first size, and the grid-stride loop takes a second trip at the second
+BIG_PARTIAL, BIG_SECOND_TRIP = 8_388_608 + 1031, 16_777_216 + 1203
+PAD, SENTINEL = 64, -77.0          # the sentinel is exact in bf16 too
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [BIG_PARTIAL, BIG_SECOND_TRIP])
+def test_adam_step_raw_bit_exact_past_the_grid_cap(n):
+    """test_adam_per_tensor_bit_exact's check on vitmi_adam_step itself, at the sizes where the plain
+    kernel's second in-flight group runs, with and without the bf16 shadow; every buffer sits PAD
+    elements into a larger allocation whose margins must come back untouched."""
+    from vitmi._lib import check, lib
+    rng = np.random.default_rng(n % 1000)
+    p0, g1, g2 = (rng.standard_normal(n, dtype=np.float32) for _ in range(3))
+    zero = np.zeros(n, np.float32)
+    s1 = optim_ref.adam_step(p0, g1, zero, zero, 1e-3, 1, grad_scale=0.5)
+    refs = (s1, optim_ref.adam_step(s1[0], g2, s1[1], s1[2], 1e-3, 2, grad_scale=0.5))
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)    # noqa: E731
+
+    def guarded(init=None, dtype=torch.float32):
+        full = torch.full((n + 2 * PAD,), SENTINEL, dtype=dtype, device=DEV)
+        if init is not None:
+            full[PAD:PAD + n] = torch.from_numpy(init).to(DEV)
+        return full
+
+    def inner(full):
+        return full[PAD:PAD + n]
+
+    grads = [guarded(g1), guarded(g2)]
+    for shadow in (False, True):
+        p, m, v = guarded(p0), guarded(zero), guarded(zero)
+        lp = guarded(dtype=torch.bfloat16) if shadow else None
+        for t, (gd, ref) in enumerate(zip(grads, refs), start=1):
+            check(lib().vitmi_adam_step(n, inner(p).data_ptr(), inner(gd).data_ptr(), inner(m).data_ptr(),
+                                        inner(v).data_ptr(), inner(lp).data_ptr() if shadow else None,
+                                        optim.keras_alpha(1e-3, 0.9, 0.999, t), 0.9, 0.999, 1e-7, 0.5,
+                                        torch.cuda.current_stream().cuda_stream), "adam_step")
+            torch.cuda.synchronize()
+            for name, buf, want in zip("pmv", (p, m, v), ref):
+                assert np.array_equal(bits(inner(buf).cpu().numpy()), bits(want)), (name, t, shadow)
+            if shadow:
+                want_lp = torch.from_numpy(ref[0]).to(torch.bfloat16).view(torch.int16)
+                assert torch.equal(inner(lp).cpu().view(torch.int16), want_lp), t
+        for buf in (p, m, v) + ((lp,) if shadow else ()):
+            assert bool((buf[:PAD] == SENTINEL).all()) and bool((buf[-PAD:] == SENTINEL).all())
+    for gd, want in zip(grads, (g1, g2)):                       # the gradients are only read
+        assert np.array_equal(bits(gd.cpu().numpy()[PAD:PAD + n]), bits(want))
+        assert bool((gd[:PAD] == SENTINEL).all()) and bool((gd[-PAD:] == SENTINEL).all())
+
+
 @pytest.mark.gpu
 def test_adam_arena_single_launch_and_bf16_shadow():
     from vitmi.config import ViTConfig

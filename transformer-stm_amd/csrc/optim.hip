@@ -32,9 +32,7 @@ __device__ __forceinline__ void adam1(const AdamArgs& a, float& p, float g, floa
   p = __fsub_rn(p, __fdiv_rn(__fmul_rn(m, a.alpha), den));
 }
 
-// streaming (non-temporal) loads and stores, ADAM_U = two 16-B groups per thread in flight:
-// 573-595 -> 504-526 us per ViT-B step (tools/ln_bench.py, same box, A/B)
-static constexpr int ADAM_U = 2;
+// streaming (non-temporal) loads and stores
 template <typename V>
 __device__ __forceinline__ V ld_s(const V* q) {
   return __builtin_nontemporal_load(q);
@@ -42,60 +40,6 @@ __device__ __forceinline__ V ld_s(const V* q) {
 template <typename V>
 __device__ __forceinline__ void st_s(V* q, V x) {
   __builtin_nontemporal_store(x, q);
-}
-
-template <bool LP>
-__global__ __launch_bounds__(256) void adam_kernel(int64_t n, float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v,
-                                                   bf16* __restrict__ lp, AdamArgs a) {
-  const int64_t n4 = n / 4;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  constexpr int U = ADAM_U;
-  for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += U * stride) {
-    f32x4 pv[U], gv[U], mv[U], vv[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t i = i0 + u * stride;
-      if (u == 0 || i < n4) {
-        pv[u] = ld_s((const f32x4*)p + i);
-        gv[u] = ld_s((const f32x4*)g + i);
-        mv[u] = ld_s((const f32x4*)m + i);
-        vv[u] = ld_s((const f32x4*)v + i);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t i = i0 + u * stride;
-      if (u > 0 && i >= n4) break;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float pe = pv[u][e], me = mv[u][e], ve = vv[u][e];
-        adam1(a, pe, gv[u][e], me, ve);
-        pv[u][e] = pe;
-        mv[u][e] = me;
-        vv[u][e] = ve;
-      }
-      st_s((f32x4*)p + i, pv[u]);
-      st_s((f32x4*)m + i, mv[u]);
-      st_s((f32x4*)v + i, vv[u]);
-      if constexpr (LP) {
-        bf16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = from_f32<bf16>(pv[u][e]);
-        ((bf16x4*)lp)[i] = o;
-      }
-    }
-  }
-  // tail (n % 4) by the first threads
-  const int64_t t = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n && t < n4 * 4 + 4) {
-    float pe = p[t], me = m[t], ve = v[t];
-    adam1(a, pe, g[t], me, ve);
-    p[t] = pe;
-    m[t] = me;
-    v[t] = ve;
-    if constexpr (LP) lp[t] = from_f32<bf16>(pe);
-  }
 }
 
 // ---------------------------------------------------------------- global-norm clipping
@@ -221,73 +165,6 @@ __device__ __forceinline__ void shadow_only(int64_t n4, int64_t first, int64_t s
   if (tail) lp[t] = from_f32<bf16>(p[t]);
 }
 
-// adam_kernel's loop with the record read once per thread.  A skipped step reads p alone and
-// writes only the shadow.  decay_mask: one byte per 64 elements (16 consecutive 16-B groups).
-template <bool LP>
-__global__ __launch_bounds__(256) void adam_ctl_kernel(int64_t n, float* __restrict__ p, const float* __restrict__ g,
-                                                       float* __restrict__ m, float* __restrict__ v,
-                                                       bf16* __restrict__ lp, AdamArgs a, float wd, float lr,
-                                                       const uint8_t* __restrict__ mask,
-                                                       const ClipCtl* __restrict__ ctl) {
-  const int64_t n4 = n / 4;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t t = n4 * 4 + first;   // tail (n % 4) by the first threads
-  const bool tail = t < n && t < n4 * 4 + 4;
-  const float coef = ctl ? ctl->coef : 1.f;
-  if (ctl && ctl->skip) {
-    if constexpr (LP) shadow_only(n4, first, stride, tail, t, p, lp);
-    return;
-  }
-  constexpr int U = ADAM_U;
-  for (int64_t i0 = first; i0 < n4; i0 += U * stride) {
-    f32x4 pv[U], gv[U], mv[U], vv[U];
-    bool dec[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t i = i0 + u * stride;
-      dec[u] = false;
-      if (u == 0 || i < n4) {
-        pv[u] = ld_s((const f32x4*)p + i);
-        gv[u] = ld_s((const f32x4*)g + i);
-        mv[u] = ld_s((const f32x4*)m + i);
-        vv[u] = ld_s((const f32x4*)v + i);
-        dec[u] = wd != 0.f && (!mask || mask[i >> 4] != 0);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t i = i0 + u * stride;
-      if (u > 0 && i >= n4) break;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float pe = pv[u][e], me = mv[u][e], ve = vv[u][e];
-        adam1_ctl(a, coef, dec[u], wd, lr, pe, gv[u][e], me, ve);
-        pv[u][e] = pe;
-        mv[u][e] = me;
-        vv[u][e] = ve;
-      }
-      st_s((f32x4*)p + i, pv[u]);
-      st_s((f32x4*)m + i, mv[u]);
-      st_s((f32x4*)v + i, vv[u]);
-      if constexpr (LP) {
-        bf16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = from_f32<bf16>(pv[u][e]);
-        ((bf16x4*)lp)[i] = o;
-      }
-    }
-  }
-  if (tail) {
-    float pe = p[t], me = m[t], ve = v[t];
-    adam1_ctl(a, coef, wd != 0.f && (!mask || mask[t >> 6] != 0), wd, lr, pe, g[t], me, ve);
-    p[t] = pe;
-    m[t] = me;
-    v[t] = ve;
-    if constexpr (LP) lp[t] = from_f32<bf16>(pe);
-  }
-}
-
 // ---------------------------------------------------------------- EMA of the weights
 // keras.optimizers.Adam(use_ema=True): e <- mom e + (1 - mom) p_new, three rounded fp32 ops on the
 // parameter the step has just produced (one_m = 1 - mom is formed on the host, in fp32).
@@ -295,27 +172,42 @@ __device__ __forceinline__ float ema1(float e, float p, float mom, float one_m) 
   return __fadd_rn(__fmul_rn(mom, e), __fmul_rn(one_m, p));
 }
 
-// adam_ctl_kernel's loop with the average as a fifth stream: 4 B read and 4 B written per parameter
-// on top of the step's.  A skipped step neither reads nor writes e.
-// Measured at the ViT-B arena (tools/ema_bench.py, two processes of three rounds each): 546-564 us as
-// written (ADAM_U = 2, streaming load of e), 580-588 us with a plain load of e, 600-604 us with one
-// 16-B group per thread in flight.
-template <bool LP>
-__global__ __launch_bounds__(256) void adam_ema_kernel(int64_t n, float* __restrict__ p, const float* __restrict__ g,
-                                                       float* __restrict__ m, float* __restrict__ v,
-                                                       bf16* __restrict__ lp, AdamArgs a, float wd, float lr,
-                                                       const uint8_t* __restrict__ mask,
-                                                       const ClipCtl* __restrict__ ctl, float* __restrict__ ema,
-                                                       float mom, float one_m) {
+// ---------------------------------------------------------------- the step kernel
+// One loop behind the three step entry points; the switches are compile-time, so an instance holds
+// nothing of the others' lines:
+//   <LP, false, false>  vitmi_adam_step: adam1; no trace of coef, decay or the record.
+//   <LP, true, false>   vitmi_adam_step_ctl: adam1_ctl, the record read once per thread.  A skipped step
+//                       reads p alone and writes only the shadow.  mask: one byte per 64 elements (16
+//                       consecutive 16-B groups).
+//   <LP, true, true>    vitmi_adam_step_ema: the same with the average as a fifth stream, 4 B read and
+//                       4 B written per parameter on top.  A skipped step neither reads nor writes e.
+// LP: the bf16 shadow of the new p, a plain 8-B store.  ADAM_U = two 16-B groups per thread in flight,
+// every load issued before the first use, non-temporal loads and stores of the fp32 streams; the
+// first threads of the grid take n % 4.  Measured at the ViT-B arena, us per step:
+//   <true, false, false> (tools/ln_bench.py, same box, A/B): 504-526 as written, 573-595 with plain
+//     loads and stores and one group in flight.
+//   <true, true, true> (tools/ema_bench.py, two processes of three rounds each): 546-564 as written,
+//     580-588 with a plain load of e, 600-604 with one group in flight.
+static constexpr int ADAM_U = 2;
+template <bool LP, bool CTL, bool EMA>
+__global__ __launch_bounds__(256) void adam_kernel(int64_t n, float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v,
+                                                   bf16* __restrict__ lp, AdamArgs a, float wd, float lr,
+                                                   const uint8_t* __restrict__ mask, const ClipCtl* __restrict__ ctl,
+                                                   float* __restrict__ ema, float mom, float one_m) {
+  static_assert(CTL || !EMA, "the average rides on the ctl step");
   const int64_t n4 = n / 4;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t t = n4 * 4 + first;   // tail (n % 4) by the first threads
   const bool tail = t < n && t < n4 * 4 + 4;
-  const float coef = ctl ? ctl->coef : 1.f;
-  if (ctl && ctl->skip) {
-    if constexpr (LP) shadow_only(n4, first, stride, tail, t, p, lp);
-    return;
+  float coef = 1.f;
+  if constexpr (CTL) {
+    coef = ctl ? ctl->coef : 1.f;
+    if (ctl && ctl->skip) {
+      if constexpr (LP) shadow_only(n4, first, stride, tail, t, p, lp);
+      return;
+    }
   }
   constexpr int U = ADAM_U;
   for (int64_t i0 = first; i0 < n4; i0 += U * stride) {
@@ -324,14 +216,14 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(int64_t n, float* __restr
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t i = i0 + u * stride;
-      dec[u] = false;
+      if constexpr (CTL) dec[u] = false;
       if (u == 0 || i < n4) {
         pv[u] = ld_s((const f32x4*)p + i);
         gv[u] = ld_s((const f32x4*)g + i);
         mv[u] = ld_s((const f32x4*)m + i);
         vv[u] = ld_s((const f32x4*)v + i);
-        ev[u] = ld_s((const f32x4*)ema + i);
-        dec[u] = wd != 0.f && (!mask || mask[i >> 4] != 0);
+        if constexpr (EMA) ev[u] = ld_s((const f32x4*)ema + i);
+        if constexpr (CTL) dec[u] = wd != 0.f && (!mask || mask[i >> 4] != 0);
       }
     }
 #pragma unroll
@@ -341,16 +233,17 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(int64_t n, float* __restr
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float pe = pv[u][e], me = mv[u][e], ve = vv[u][e];
-        adam1_ctl(a, coef, dec[u], wd, lr, pe, gv[u][e], me, ve);
+        if constexpr (CTL) adam1_ctl(a, coef, dec[u], wd, lr, pe, gv[u][e], me, ve);
+        else adam1(a, pe, gv[u][e], me, ve);
         pv[u][e] = pe;
         mv[u][e] = me;
         vv[u][e] = ve;
-        ev[u][e] = ema1(ev[u][e], pe, mom, one_m);
+        if constexpr (EMA) ev[u][e] = ema1(ev[u][e], pe, mom, one_m);
       }
       st_s((f32x4*)p + i, pv[u]);
       st_s((f32x4*)m + i, mv[u]);
       st_s((f32x4*)v + i, vv[u]);
-      st_s((f32x4*)ema + i, ev[u]);
+      if constexpr (EMA) st_s((f32x4*)ema + i, ev[u]);
       if constexpr (LP) {
         bf16x4 o;
 #pragma unroll
@@ -361,11 +254,12 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(int64_t n, float* __restr
   }
   if (tail) {
     float pe = p[t], me = m[t], ve = v[t];
-    adam1_ctl(a, coef, wd != 0.f && (!mask || mask[t >> 6] != 0), wd, lr, pe, g[t], me, ve);
+    if constexpr (CTL) adam1_ctl(a, coef, wd != 0.f && (!mask || mask[t >> 6] != 0), wd, lr, pe, g[t], me, ve);
+    else adam1(a, pe, g[t], me, ve);
     p[t] = pe;
     m[t] = me;
     v[t] = ve;
-    ema[t] = ema1(ema[t], pe, mom, one_m);
+    if constexpr (EMA) ema[t] = ema1(ema[t], pe, mom, one_m);
     if constexpr (LP) lp[t] = from_f32<bf16>(pe);
   }
 }
@@ -405,23 +299,45 @@ __global__ __launch_bounds__(256) void ema_apply_kernel(int64_t n, float* __rest
 
 using namespace vitmi;
 
-extern "C" int vitmi_adam_step(int64_t n, float* p, const float* g, float* m, float* v, void* p_lp, float alpha,
-                               double beta_1, double beta_2, float epsilon, float grad_scale, vitmi_stream_t stream) {
-  VITMI_CHECK_ARG(n >= 0, "adam_step: n < 0");
-  if (n == 0) return VITMI_OK;
-  VITMI_CHECK_ARG(p && g && m && v, "adam_step: null pointer");
-  VITMI_CHECK_ARG(aligned_to(p, 16) && aligned_to(g, 16) && aligned_to(m, 16) && aligned_to(v, 16),
-                  "adam_step: fp32 buffers must be 16-byte aligned");
-  VITMI_CHECK_ARG(aligned_to(p_lp, 8), "adam_step: bf16 shadow must be 8-byte aligned");
+// What the three step entry points share: every check, the arguments, the recorded bytes and the
+// launch.  `what` is the entry point's name; ctl_form / ema_form say which instance it runs, whatever
+// the values (vitmi_adam_step passes weight_decay 0 and null decay_mask, ctl and ema).  Value
+// arguments are judged before the n == 0 return, pointers after it.
+static int adam_launch(const char* what, bool ctl_form, bool ema_form, int64_t n, float* p, const float* g, float* m,
+                       float* v, void* p_lp, float alpha, double beta_1, double beta_2, float epsilon,
+                       float grad_scale, float weight_decay, float lr, const uint8_t* decay_mask, const void* ctl,
+                       float* ema, float ema_momentum, vitmi_stream_t stream) {
+  VITMI_CHECK_ARG(n >= 0, "%s: n < 0", what);
   VITMI_CHECK_ARG(beta_1 >= 0.0 && beta_1 < 1.0 && beta_2 >= 0.0 && beta_2 < 1.0 && epsilon >= 0.f,
-                  "adam_step: bad hyper-parameters");
+                  "%s: bad hyper-parameters", what);
+  VITMI_CHECK_ARG(weight_decay >= 0.f, "%s: weight_decay must be >= 0", what);
+  VITMI_CHECK_ARG(ema_momentum >= 0.f && ema_momentum < 1.f, "%s: ema_momentum must be in [0, 1)", what);
+  if (n == 0) return VITMI_OK;
+  VITMI_CHECK_ARG(p && g && m && v && (ema || !ema_form), "%s: null pointer", what);
+  VITMI_CHECK_ARG(aligned_to(p, 16) && aligned_to(g, 16) && aligned_to(m, 16) && aligned_to(v, 16) &&
+                      aligned_to(ema, 16),
+                  "%s: fp32 buffers must be 16-byte aligned", what);
+  VITMI_CHECK_ARG(aligned_to(p_lp, 8), "%s: bf16 shadow must be 8-byte aligned", what);
+  VITMI_CHECK_ARG(aligned_to(ctl, 16), "%s: the clip record must be 16-byte aligned", what);
   // (1 - beta) in double then rounded once, as Keras does with its Python-float hyper-parameters
   AdamArgs a{alpha, (float)(1.0 - beta_1), (float)(1.0 - beta_2), epsilon, grad_scale};
-  // p, g, m, v read; p, m, v (+ the bf16 shadow) written
-  launch(p_lp ? adam_kernel<true> : adam_kernel<false>, dim3(grid_cap(n / 4)), dim3(256), (hipStream_t)stream, 0,
-         (double)n * (p_lp ? 30 : 28), n, p, g, m, v, (bf16*)p_lp, a);
-  VITMI_LAUNCH_CHECK("adam_step");
+  // p, g, m, v (+ the average) read; p, m, v (+ the average, + the bf16 shadow) written; plus the mask
+  // bytes and the record (a skipped step moves less: not known here)
+  const double bytes = (double)n * ((ema_form ? 36 : 28) + (p_lp ? 2 : 0)) +
+                       (decay_mask && weight_decay != 0.f ? (double)((n + 63) / 64) : 0.0) + (ctl ? 16.0 : 0.0);
+  auto kernel = ema_form   ? (p_lp ? adam_kernel<true, true, true> : adam_kernel<false, true, true>)
+                : ctl_form ? (p_lp ? adam_kernel<true, true, false> : adam_kernel<false, true, false>)
+                           : (p_lp ? adam_kernel<true, false, false> : adam_kernel<false, false, false>);
+  launch(kernel, dim3(grid_cap(n / 4)), dim3(256), (hipStream_t)stream, 0, bytes, n, p, g, m, v, (bf16*)p_lp, a,
+         weight_decay, lr, decay_mask, (const ClipCtl*)ctl, ema, ema_momentum, 1.f - ema_momentum);
+  VITMI_LAUNCH_CHECK(what);
   return VITMI_OK;
+}
+
+extern "C" int vitmi_adam_step(int64_t n, float* p, const float* g, float* m, float* v, void* p_lp, float alpha,
+                               double beta_1, double beta_2, float epsilon, float grad_scale, vitmi_stream_t stream) {
+  return adam_launch("adam_step", false, false, n, p, g, m, v, p_lp, alpha, beta_1, beta_2, epsilon, grad_scale, 0.f,
+                     0.f, nullptr, nullptr, nullptr, 0.f, stream);
 }
 
 extern "C" size_t vitmi_grad_sumsq_partials(int64_t n) {
@@ -460,50 +376,16 @@ extern "C" int vitmi_clip_finalize(int64_t n_partials, const double* partials, f
 extern "C" int vitmi_adam_step_ctl(int64_t n, float* p, const float* g, float* m, float* v, void* p_lp, float alpha,
                                    double beta_1, double beta_2, float epsilon, float grad_scale, float weight_decay,
                                    float lr, const uint8_t* decay_mask, const void* ctl, vitmi_stream_t stream) {
-  VITMI_CHECK_ARG(n >= 0, "adam_step_ctl: n < 0");
-  if (n == 0) return VITMI_OK;
-  VITMI_CHECK_ARG(p && g && m && v, "adam_step_ctl: null pointer");
-  VITMI_CHECK_ARG(aligned_to(p, 16) && aligned_to(g, 16) && aligned_to(m, 16) && aligned_to(v, 16),
-                  "adam_step_ctl: fp32 buffers must be 16-byte aligned");
-  VITMI_CHECK_ARG(aligned_to(p_lp, 8), "adam_step_ctl: bf16 shadow must be 8-byte aligned");
-  VITMI_CHECK_ARG(aligned_to(ctl, 16), "adam_step_ctl: the clip record must be 16-byte aligned");
-  VITMI_CHECK_ARG(beta_1 >= 0.0 && beta_1 < 1.0 && beta_2 >= 0.0 && beta_2 < 1.0 && epsilon >= 0.f,
-                  "adam_step_ctl: bad hyper-parameters");
-  VITMI_CHECK_ARG(weight_decay >= 0.f, "adam_step_ctl: weight_decay must be >= 0");
-  AdamArgs a{alpha, (float)(1.0 - beta_1), (float)(1.0 - beta_2), epsilon, grad_scale};
-  // as adam_step, plus the mask bytes and the record (a skipped step moves less: not known here)
-  const double extra = (decay_mask && weight_decay != 0.f ? (double)((n + 63) / 64) : 0.0) + (ctl ? 16.0 : 0.0);
-  launch(p_lp ? adam_ctl_kernel<true> : adam_ctl_kernel<false>, dim3(grid_cap(n / 4)), dim3(256), (hipStream_t)stream,
-         0, (double)n * (p_lp ? 30 : 28) + extra, n, p, g, m, v, (bf16*)p_lp, a, weight_decay, lr, decay_mask,
-         (const ClipCtl*)ctl);
-  VITMI_LAUNCH_CHECK("adam_step_ctl");
-  return VITMI_OK;
+  return adam_launch("adam_step_ctl", true, false, n, p, g, m, v, p_lp, alpha, beta_1, beta_2, epsilon, grad_scale,
+                     weight_decay, lr, decay_mask, ctl, nullptr, 0.f, stream);
 }
 
 extern "C" int vitmi_adam_step_ema(int64_t n, float* p, const float* g, float* m, float* v, void* p_lp, float alpha,
                                    double beta_1, double beta_2, float epsilon, float grad_scale, float weight_decay,
                                    float lr, const uint8_t* decay_mask, const void* ctl, float* ema,
                                    float ema_momentum, vitmi_stream_t stream) {
-  VITMI_CHECK_ARG(n >= 0, "adam_step_ema: n < 0");
-  VITMI_CHECK_ARG(beta_1 >= 0.0 && beta_1 < 1.0 && beta_2 >= 0.0 && beta_2 < 1.0 && epsilon >= 0.f,
-                  "adam_step_ema: bad hyper-parameters");
-  VITMI_CHECK_ARG(weight_decay >= 0.f, "adam_step_ema: weight_decay must be >= 0");
-  VITMI_CHECK_ARG(ema_momentum >= 0.f && ema_momentum < 1.f, "adam_step_ema: ema_momentum must be in [0, 1)");
-  if (n == 0) return VITMI_OK;
-  VITMI_CHECK_ARG(p && g && m && v && ema, "adam_step_ema: null pointer");
-  VITMI_CHECK_ARG(aligned_to(p, 16) && aligned_to(g, 16) && aligned_to(m, 16) && aligned_to(v, 16) &&
-                      aligned_to(ema, 16),
-                  "adam_step_ema: fp32 buffers must be 16-byte aligned");
-  VITMI_CHECK_ARG(aligned_to(p_lp, 8), "adam_step_ema: bf16 shadow must be 8-byte aligned");
-  VITMI_CHECK_ARG(aligned_to(ctl, 16), "adam_step_ema: the clip record must be 16-byte aligned");
-  AdamArgs a{alpha, (float)(1.0 - beta_1), (float)(1.0 - beta_2), epsilon, grad_scale};
-  // as adam_step_ctl, plus the average read and written
-  const double extra = (decay_mask && weight_decay != 0.f ? (double)((n + 63) / 64) : 0.0) + (ctl ? 16.0 : 0.0);
-  launch(p_lp ? adam_ema_kernel<true> : adam_ema_kernel<false>, dim3(grid_cap(n / 4)), dim3(256), (hipStream_t)stream,
-         0, (double)n * (p_lp ? 38 : 36) + extra, n, p, g, m, v, (bf16*)p_lp, a, weight_decay, lr, decay_mask,
-         (const ClipCtl*)ctl, ema, ema_momentum, 1.f - ema_momentum);
-  VITMI_LAUNCH_CHECK("adam_step_ema");
-  return VITMI_OK;
+  return adam_launch("adam_step_ema", true, true, n, p, g, m, v, p_lp, alpha, beta_1, beta_2, epsilon, grad_scale,
+                     weight_decay, lr, decay_mask, ctl, ema, ema_momentum, stream);
 }
 
 extern "C" int vitmi_ema_apply(int64_t n, float* p, float* ema, void* p_lp, int mode, vitmi_stream_t stream) {

@@ -220,36 +220,30 @@ class Adam:
         ctl = self._ctl_record()
         return ctl[1], ctl[0]
 
+    def _step_call(self, n: int, p, g, m, v, lp, alpha: float, lr: float, wd: float, mask, ctl, ema, mom) -> None:
+        """One step launch over n elements; every buffer is a raw pointer or None.  The plain step
+        when the optimizer has no average, no record and no weight decay, else the step with the
+        average when there is one, else the step with the record, the decay or both."""
+        head = (n, p, g, m, v, lp, alpha, self.beta_1, self.beta_2, self.epsilon, self.grad_scale)
+        if ema is None and ctl is None and self.weight_decay == 0.0:
+            check(lib().vitmi_adam_step(*head, ops._s()), "adam_step")
+        elif ema is not None:
+            check(lib().vitmi_adam_step_ema(*head, wd, lr, mask, ctl, ema, mom, ops._s()), "adam_step_ema")
+        else:
+            check(lib().vitmi_adam_step_ctl(*head, wd, lr, mask, ctl, ops._s()), "adam_step_ctl")
+
     def _launch(self, s0: int, e0: int, alpha: float, lr: Optional[float] = None,
                 ctl: Optional[Tensor] = None, mom: Optional[float] = None) -> None:
         arena, lp = self._arena, self._arena.flat_lp
-        if self._ema is None and ctl is None and self.weight_decay == 0.0:
-            check(lib().vitmi_adam_step(e0 - s0, ops._p(arena.flat[s0:]), ops._p(arena.grad[s0:]),
-                                        ops._p(self._m[s0:]), ops._p(self._v[s0:]),
-                                        ops._p(lp[s0:]) if lp is not None else None, alpha,
-                                        self.beta_1, self.beta_2, self.epsilon, self.grad_scale, ops._s()),
-                  "adam_step")
-            return
         mask = None
         if self.weight_decay != 0.0:
             if s0 % arena.ALIGN:
                 raise RuntimeError("vitmi Adam: weight decay needs step ranges on 64-element boundaries")
             mask = ops._p(self._decay_mask()[s0 // arena.ALIGN:])
-        if self._ema is not None:
-            check(lib().vitmi_adam_step_ema(e0 - s0, ops._p(arena.flat[s0:]), ops._p(arena.grad[s0:]),
-                                            ops._p(self._m[s0:]), ops._p(self._v[s0:]),
-                                            ops._p(lp[s0:]) if lp is not None else None, alpha,
-                                            self.beta_1, self.beta_2, self.epsilon, self.grad_scale,
-                                            self.weight_decay, self.learning_rate if lr is None else lr, mask,
-                                            ops._p(ctl), ops._p(self._ema[s0:]), mom, ops._s()),
-                  "adam_step_ema")
-            return
-        check(lib().vitmi_adam_step_ctl(e0 - s0, ops._p(arena.flat[s0:]), ops._p(arena.grad[s0:]),
-                                        ops._p(self._m[s0:]), ops._p(self._v[s0:]),
-                                        ops._p(lp[s0:]) if lp is not None else None, alpha,
-                                        self.beta_1, self.beta_2, self.epsilon, self.grad_scale, self.weight_decay,
-                                        self.learning_rate if lr is None else lr, mask, ops._p(ctl), ops._s()),
-              "adam_step_ctl")
+        self._step_call(e0 - s0, ops._p(arena.flat[s0:]), ops._p(arena.grad[s0:]), ops._p(self._m[s0:]),
+                        ops._p(self._v[s0:]), ops._p(lp[s0:]) if lp is not None else None, alpha,
+                        self.learning_rate if lr is None else lr, self.weight_decay, mask, ops._p(ctl),
+                        ops._p(self._ema[s0:]) if self._ema is not None else None, mom)
 
     @torch.no_grad()
     def _on_bucket(self, s0: int, e0: int, stream) -> None:
@@ -350,24 +344,12 @@ class Adam:
         ctl = self._clip([(p.grad, p.numel()) for p, _, _, _ in todo]) if self._use_ctl() else None
         emas = {id(p): e for p, e in zip(self.params, self._ema)} if self._ema is not None else {}
         for p, m, v, dec in todo:
-            if self._ema is not None:
-                check(lib().vitmi_adam_step_ema(p.numel(), ops._p(p), ops._p(p.grad), ops._p(m), ops._p(v), None,
-                                                alpha, self.beta_1, self.beta_2, self.epsilon, self.grad_scale,
-                                                self.weight_decay if dec else 0.0, self.learning_rate, None,
-                                                ops._p(ctl), ops._p(emas[id(p)]), mom, ops._s()), "adam_step_ema")
-                if overwrite:
-                    check(lib().vitmi_ema_apply(p.numel(), ops._p(p), ops._p(emas[id(p)]), None, 1, ops._s()),
-                          "ema_apply")
-            elif ctl is None and self.weight_decay == 0.0:
-                check(lib().vitmi_adam_step(p.numel(), ops._p(p), ops._p(p.grad), ops._p(m), ops._p(v), None, alpha,
-                                            self.beta_1, self.beta_2, self.epsilon, self.grad_scale, ops._s()),
-                      "adam_step")
-            else:
-                # a decaying tensor decays whole (NULL mask); one that does not gets weight_decay 0
-                check(lib().vitmi_adam_step_ctl(p.numel(), ops._p(p), ops._p(p.grad), ops._p(m), ops._p(v), None,
-                                                alpha, self.beta_1, self.beta_2, self.epsilon, self.grad_scale,
-                                                self.weight_decay if dec else 0.0, self.learning_rate, None,
-                                                ops._p(ctl), ops._s()), "adam_step_ctl")
+            # a decaying tensor decays whole (NULL mask); one that does not gets weight_decay 0
+            e = ops._p(emas[id(p)]) if self._ema is not None else None
+            self._step_call(p.numel(), ops._p(p), ops._p(p.grad), ops._p(m), ops._p(v), None, alpha,
+                            self.learning_rate, self.weight_decay if dec else 0.0, None, ops._p(ctl), e, mom)
+            if overwrite:
+                check(lib().vitmi_ema_apply(p.numel(), ops._p(p), e, None, 1, ops._s()), "ema_apply")
             # the kernel wrote through a raw pointer: bump the version counter, so a ParamArena
             # that owns p (its bf16 operand shadow is keyed on these counters) re-casts it
             torch.autograd.graph.increment_version(p)
