@@ -256,14 +256,20 @@ int vitmi_attention_bwd_bias(int dtype, int B, int N, int H, int dh, float scale
  * old_codes/MS_CvT.py:352-361): im2col of the fp32 NCHW images into
  * patches [B*(S/P)^2][C*P*P] of `dtype` (column order c, kh, kw = the conv weight's).
  * Limits: S % P == 0, P % 4 == 0, C*P*P <= 4096 (one thread per 4 columns of a patch row).
+ * dtype is VITMI_F32 or VITMI_BF16 (any other is refused: the kernels write nothing else); B >= 0
+ * (B == 0 does nothing), C > 0, S > 0; img 16-byte aligned, patches 16-byte (fp32) or 8-byte (bf16)
+ * aligned.
  */
 int vitmi_patch_im2col(int dtype, int B, int C, int S, int P, const float* img, void* patches,
                        vitmi_stream_t stream);
-/* x[b][0] = cls + pos[0];  x[b][1+p] = tok[b*np+p] + pos[1+p]   (cls/pos may be NULL) */
+/* x[b][0] = cls + pos[0];  x[b][1+p] = tok[b*np+p] + pos[1+p]   (cls/pos may be NULL).
+ * B >= 0, np >= 0, D > 0 and D % 4 == 0; every pointer given is 16-byte aligned. */
 int vitmi_tokens_assemble(int B, int np, int D, const float* tok, const float* cls,
                           const float* pos, float* x, vitmi_stream_t stream);
 /* backward of assemble: dtok (f32, and optional bf16 copy) = dx[:,1:];  dpos += sum_b dx,
- * dcls += sum_b dx[:,0]   (NULL pointers skip that output) */
+ * dcls += sum_b dx[:,0]   (NULL pointers skip that output).  The sums run over b = 0, 1, ... in
+ * order from 0 and are added to what dpos / dcls hold (bitwise reproducible).  B >= 0, np >= 0,
+ * D > 0 and D % 4 == 0; every pointer given is 16-byte aligned (dtok_lp: 8-byte). */
 int vitmi_tokens_assemble_bwd(int B, int np, int D, const float* dx, float* dtok, void* dtok_lp,
                               float* dcls, float* dpos, vitmi_stream_t stream);
 
@@ -277,7 +283,9 @@ int vitmi_tokens_assemble_bwd(int B, int np, int D, const float* dx, float* dtok
  *   patches (out, saved for the backward) = im2col(img) [B*np][C*P*P] of dtype, np = (S/P)^2;
  *   x (out, fp32 [B][np+1][D]) = [cls ; patches W^T + bias] + pos   (cls/pos/bias may be NULL);
  *   w: [D][C*P*P] of dtype (the conv weight flattened).
- * vitmi_patch_embed_bwd: dW += ..., dbias += ..., dcls += ..., dpos += ... from dx (NULL skips). */
+ * vitmi_patch_embed_bwd: dW += ..., dbias += ..., dcls += ..., dpos += ... from dx (NULL skips).
+ * dtype is VITMI_F32 or VITMI_BF16 in all of these (and in the _keep forms); any other is refused and
+ * its workspace query returns 0: the split operand dtypes take an fp32 im2col followed by a split. */
 size_t vitmi_patch_embed_fwd_workspace_size(int dtype, int B, int C, int S, int P, int D);
 int vitmi_patch_embed_fwd(int dtype, int B, int C, int S, int P, int D, const float* img, const void* w,
                           const float* bias, const float* cls, const float* pos, void* patches, float* x,
@@ -303,14 +311,16 @@ int vitmi_mse_bwd(int B, int C, const float* pred, const float* target, float* d
 /* ---------------------------------------------------------------------------
  * Head (layers.Dense(num_classes) on LN(cls), models/CvT(Par).py:326-329,350) and loss
  * (compile(loss='mean_squared_error') :464-466; softmax-CE for >=2 classes).
- * y: fp32 [B][ldy]; W fp32 [C][D].
+ * y: fp32 [B][ldy]; W fp32 [C][D].  Both calls need B > 0, C > 0, D > 0 and ldy >= D.
  */
 int vitmi_head_fwd(int B, int D, int C, const float* y, int64_t ldy, const float* w,
                    const float* b, float* logits, vitmi_stream_t stream);
 int vitmi_head_bwd(int B, int D, int C, const float* dlogits, const float* y, int64_t ldy,
                    const float* w, float* dy, float* dw, float* db, vitmi_stream_t stream);
 /* loss = mean over batch; dlogits = d loss / d logits.  target: int64 [B] (CE) or f32 [B][C] (MSE).
- * Either output may be NULL (not both). */
+ * Either output may be NULL (not both).  A CE label outside [0, C) matches no class (as in
+ * vitmi_softmax_xent): the row's loss is its log-sum-exp, its gradient softmax / B, and no logit is
+ * read at the label. */
 int vitmi_loss_fwd_bwd(int kind, int B, int C, const float* logits, const void* target,
                        float* loss, float* dlogits, vitmi_stream_t stream);
 
@@ -332,7 +342,7 @@ int vitmi_linear_fwd_dropout(int dtype, int64_t M, int64_t N, int64_t K, const v
                              uint32_t seed, uint32_t site, uint32_t thresh, float scale,
                              vitmi_stream_t stream);
 /* y[M][ldy] (f32 or bf16) = x[M][ldx] (f32) * keep * scale   (N % 4 == 0): the masked
- * gradient of a dropped branch in the backward */
+ * gradient of a dropped branch in the backward.  M >= 0 and N >= 0 (either 0 does nothing). */
 int vitmi_dropout_apply(int64_t M, int64_t N, const float* x, int64_t ldx, void* y, int y_dtype,
                         int64_t ldy, uint32_t seed, uint32_t site, uint32_t thresh, float scale,
                         vitmi_stream_t stream);
@@ -704,9 +714,10 @@ int vitmi_split_bf16f8_weights(int n, const float* const* srcs, void* const* dst
 int vitmi_split_bf16f8_weights_mixed(int n, const float* const* srcs, void* const* dsts, const int64_t* rows,
                                      const int64_t* K, const int* patterns, vitmi_stream_t stream);
 
-/* fp32 -> bf16 cast of n elements (weight shadows for the bf16 MFMA path) */
+/* fp32 -> bf16 cast of n >= 0 elements (weight shadows for the bf16 MFMA path); src and dst 16-byte aligned */
 int vitmi_cast_f32_bf16(int64_t n, const float* src, void* dst, vitmi_stream_t stream);
-/* bf16 -> fp32 cast of n elements (the bf16 gradient all-reduce writes back into the fp32 arena) */
+/* bf16 -> fp32 cast of n >= 0 elements (the bf16 gradient all-reduce writes back into the fp32 arena);
+ * src and dst 16-byte aligned */
 int vitmi_cast_bf16_f32(int64_t n, const void* src, float* dst, vitmi_stream_t stream);
 
 /* ---------------------------------------------------------------------------

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import ref_tokens as rt
 from vitmi import ops
 
 pytestmark = pytest.mark.gpu
@@ -60,9 +61,20 @@ def test_patch_embed_entry_points(dtype, B, C, S, P, D):
     r = torch.cat([cl.expand(B, 1, D), r], 1) + pl
     r.backward(dx.to(dtype).float() if dtype != torch.float32 else dx)
     gtol = 1e-4 if dtype == torch.float32 else 2e-2
-    for got, leaf in zip(grads, (wl, bl, cl, pl)):
+    for got, leaf in zip(grads[:2], (wl, bl)):
         ref_g = leaf.grad.reshape(got.shape)
         assert (got.cpu() - ref_g).norm() <= gtol * ref_g.norm()
+    # dcls, dpos: sums of the fp32 dx over the batch, judged per element (tests/ref_tokens.py: the bound
+    # (B + 1) u sum_b|dx|, and the in-order float32 sum bit for bit)
+    zero = torch.zeros(G * G + 1, D)
+    per = rt.pos_bwd(dx.reshape(B, -1), zero, zero[0], B, G * G, D)
+    for name, got, leaf in (("dcls", grads[2], cl), ("dpos", grads[3], pl)):
+        exact, ref_g, tol_g = per[name]
+        got = got.cpu().view(exact.shape)
+        assert rt.worst_ratio(got, ref_g, tol_g) <= 1.0, name
+        assert torch.equal(got, exact), name
+        if dtype == torch.float32:     # autograd's own gradient (for bf16 it sums the rounded dx)
+            assert rt.worst_ratio(leaf.grad.reshape(exact.shape), ref_g, tol_g) <= 1.0, name
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 import ref_patchdrop as ref  # noqa: E402
+import ref_tokens  # noqa: E402
 from oracle import vit_ref  # noqa: E402
 from vitmi import ops, optim  # noqa: E402
 from vitmi.config import ViTConfig  # noqa: E402
@@ -98,11 +99,24 @@ def test_gathered_embed(dtype, near_full, B, C, S, P, D):
     leaves = [t.clone().requires_grad_(True) for t in (wr, b, cls, pos)]
     gathered(*leaves).backward(dx.to(dtype).float() if dtype != F32 else dx)
     gtol = 1e-4 if dtype == F32 else 2e-2
-    for name, got, leaf in zip(("dW", "dbias", "dcls", "dpos"), grads, leaves):
+    for name, got, leaf in zip(("dW", "dbias"), grads, leaves):
         ref_g = leaf.grad.reshape(got.shape)
         rel = ((got.cpu() - ref_g).norm() / ref_g.norm()).item()
         print(f"  {name}: rel {rel:.3e} (bound {gtol:.0e})")
         assert (got.cpu() - ref_g).norm() <= gtol * ref_g.norm()
+    # dcls, dpos: sums of the fp32 dx over the samples that kept the patch, judged per element
+    # (tests/ref_tokens.py: the bound (B + 1) u sum_b|dx|, and the in-order float32 sum bit for bit)
+    zero = torch.zeros(np_ + 1, D)
+    per = ref_tokens.pos_bwd(dx.reshape(B, -1), zero, zero[0], B, np_, D, ref.slot_indices(kn, np_))
+    for name, got, leaf in (("dcls", grads[2], leaves[2]), ("dpos", grads[3], leaves[3])):
+        exact, ref_g, tol_g = per[name]
+        got = got.cpu().view(exact.shape)
+        ratio = ref_tokens.worst_ratio(got, ref_g, tol_g)
+        print(f"  {name}: worst |err|/tol {ratio:.3f}")
+        assert ratio <= 1.0, name
+        assert torch.equal(got, exact), name
+        if dtype == F32:               # autograd's own gradient (for bf16 it sums the rounded dx)
+            assert ref_tokens.worst_ratio(leaf.grad.reshape(exact.shape), ref_g, tol_g) <= 1.0, name
     # position rows of patches no sample kept: exactly zero
     unkept = np.where((ref.slot_indices(kn, np_) >= 0).sum(axis=0) == 0)[0]
     assert near_full or len(unkept) > 0

@@ -19,7 +19,11 @@ struct PatchGeom {
 
 // keep: the patch-dropout form (csrc/patchdrop.hip), the same composition over rows = B * keep_n
 // gathered rows; the patch GEMM runs at M = B * keep_n
-int patch_geom(int B, int C, int S, int P, int D, bool keep, int keep_n, PatchGeom& g) {
+// dtype: VITMI_F32 or VITMI_BF16 only (the im2col kernels write nothing else; the split operand dtypes
+// go through an im2col to fp32 followed by a split, vitmi/modules.py)
+int patch_geom(int dtype, int B, int C, int S, int P, int D, bool keep, int keep_n, PatchGeom& g) {
+  VITMI_CHECK_ARG(dtype == VITMI_F32 || dtype == VITMI_BF16, "patch_embed: dtype must be VITMI_F32 or VITMI_BF16 "
+                  "(got %d)", dtype);
   VITMI_CHECK_ARG(B > 0 && C > 0 && D > 0 && P > 0 && S % P == 0, "patch_embed: bad shape");
   VITMI_CHECK_ARG(D % 4 == 0, "patch_embed: D %% 4 != 0");
   g.np = (int64_t)(S / P) * (S / P);
@@ -94,29 +98,29 @@ int embed_bwd(const char* what, const PatchGeom& g, int dtype, int B, int D, int
 // the same over the kept patches only (patch dropout)
 extern "C" size_t vitmi_patch_embed_fwd_workspace_size(int dtype, int B, int C, int S, int P, int D) {
   PatchGeom g;
-  return patch_geom(B, C, S, P, D, false, 0, g) ? 0 : embed_fwd_ws(dtype, g, D);
+  return patch_geom(dtype, B, C, S, P, D, false, 0, g) ? 0 : embed_fwd_ws(dtype, g, D);
 }
 
 extern "C" size_t vitmi_patch_embed_keep_fwd_workspace_size(int dtype, int B, int C, int S, int P, int D, int K) {
   PatchGeom g;
-  return patch_geom(B, C, S, P, D, true, K, g) ? 0 : embed_fwd_ws(dtype, g, D);
+  return patch_geom(dtype, B, C, S, P, D, true, K, g) ? 0 : embed_fwd_ws(dtype, g, D);
 }
 
 extern "C" size_t vitmi_patch_embed_bwd_workspace_size(int dtype, int B, int C, int S, int P, int D) {
   PatchGeom g;
-  return patch_geom(B, C, S, P, D, false, 0, g) ? 0 : embed_bwd_ws(dtype, g, D);
+  return patch_geom(dtype, B, C, S, P, D, false, 0, g) ? 0 : embed_bwd_ws(dtype, g, D);
 }
 
 extern "C" size_t vitmi_patch_embed_keep_bwd_workspace_size(int dtype, int B, int C, int S, int P, int D, int K) {
   PatchGeom g;
-  return patch_geom(B, C, S, P, D, true, K, g) ? 0 : embed_bwd_ws(dtype, g, D);
+  return patch_geom(dtype, B, C, S, P, D, true, K, g) ? 0 : embed_bwd_ws(dtype, g, D);
 }
 
 extern "C" int vitmi_patch_embed_fwd(int dtype, int B, int C, int S, int P, int D, const float* img, const void* w,
                                      const float* bias, const float* cls, const float* pos, void* patches, float* x,
                                      void* workspace, size_t ws_bytes, vitmi_stream_t stream) {
   PatchGeom g;
-  if (int rc = patch_geom(B, C, S, P, D, false, 0, g)) return rc;
+  if (int rc = patch_geom(dtype, B, C, S, P, D, false, 0, g)) return rc;
   VITMI_CHECK_ARG(img && w && patches && x, "patch_embed_fwd: null pointer");
   return embed_fwd("patch_embed_fwd", g, dtype, B, C, S, P, D, 0, nullptr, img, w, bias, cls, pos, patches, x,
                    workspace, ws_bytes, stream);
@@ -127,7 +131,7 @@ extern "C" int vitmi_patch_embed_keep_fwd(int dtype, int B, int C, int S, int P,
                                           const float* pos, void* patches, float* x, void* workspace,
                                           size_t ws_bytes, vitmi_stream_t stream) {
   PatchGeom g;
-  if (int rc = patch_geom(B, C, S, P, D, true, K, g)) return rc;
+  if (int rc = patch_geom(dtype, B, C, S, P, D, true, K, g)) return rc;
   VITMI_CHECK_ARG(keep && img && w && patches && x, "patch_embed_keep_fwd: null pointer");
   return embed_fwd("patch_embed_keep_fwd", g, dtype, B, C, S, P, D, K, keep, img, w, bias, cls, pos, patches, x,
                    workspace, ws_bytes, stream);
@@ -137,7 +141,7 @@ extern "C" int vitmi_patch_embed_bwd(int dtype, int B, int C, int S, int P, int 
                                      const void* patches, float* dw, float* dbias, float* dcls, float* dpos,
                                      void* workspace, size_t ws_bytes, vitmi_stream_t stream) {
   PatchGeom g;
-  if (int rc = patch_geom(B, C, S, P, D, false, 0, g)) return rc;
+  if (int rc = patch_geom(dtype, B, C, S, P, D, false, 0, g)) return rc;
   VITMI_CHECK_ARG(dx && patches, "patch_embed_bwd: null pointer");
   return embed_bwd("patch_embed_bwd", g, dtype, B, D, 0, nullptr, dx, patches, dw, dbias, dcls, dpos, workspace,
                    ws_bytes, stream);
@@ -148,7 +152,7 @@ extern "C" int vitmi_patch_embed_keep_bwd(int dtype, int B, int C, int S, int P,
                                           float* dcls, float* dpos, void* workspace, size_t ws_bytes,
                                           vitmi_stream_t stream) {
   PatchGeom g;
-  if (int rc = patch_geom(B, C, S, P, D, true, K, g)) return rc;
+  if (int rc = patch_geom(dtype, B, C, S, P, D, true, K, g)) return rc;
   VITMI_CHECK_ARG(slot && dx && patches, "patch_embed_keep_bwd: null pointer");
   return embed_bwd("patch_embed_keep_bwd", g, dtype, B, D, K, slot, dx, patches, dw, dbias, dcls, dpos, workspace,
                    ws_bytes, stream);

@@ -345,7 +345,9 @@ __global__ void loss_kernel(int kind, int B, int C, const float* __restrict__ lo
       float se = 0.f;
       for (int c = 0; c < C; ++c) se += expf(z[c] - mx);
       const float lse = mx + logf(se);
-      acc += lse - z[t];
+      // a label outside [0, C) matches no class: the row loss is lse, z[t] is not read
+      const bool hit = t >= 0 && t < C;
+      acc += hit ? lse - z[t] : lse;
       if (dl)
         for (int c = 0; c < C; ++c) dl[(int64_t)b * C + c] = (expf(z[c] - lse) - (c == t ? 1.f : 0.f)) * invB;
     } else {  // MSE over all outputs (Keras mean_squared_error, C == 1 for the reference)
@@ -468,8 +470,13 @@ using namespace vitmi;
 
 extern "C" int vitmi_patch_im2col(int dtype, int B, int C, int S, int P, const float* img,
                                   void* patches, vitmi_stream_t stream) {
+  VITMI_CHECK_ARG(dtype == VITMI_F32 || dtype == VITMI_BF16, "im2col: dtype must be VITMI_F32 or VITMI_BF16 (got %d)",
+                  dtype);
+  VITMI_CHECK_ARG(B >= 0 && C > 0 && S > 0, "im2col: need B >= 0, C > 0 and S > 0 (got B = %d, C = %d, S = %d)", B, C, S);
   VITMI_CHECK_ARG(P > 0 && S % P == 0 && P % 4 == 0, "im2col: need S %% P == 0 and P %% 4 == 0");
   VITMI_CHECK_ARG(img && patches, "im2col: null pointer");
+  VITMI_CHECK_ARG(aligned_to(img, 16) && aligned_to(patches, dtype == VITMI_BF16 ? 8 : 16),
+                  "im2col: img must be 16-byte aligned, patches 16-byte (fp32) or 8-byte (bf16) aligned");
   const int K = C * P * P;
   const int64_t rows = (int64_t)B * (S / P) * (S / P);
   VITMI_CHECK_ARG(K / 4 <= 1024 && rows < 0x7fffffff, "im2col: C*P*P must be <= 4096");
@@ -484,7 +491,12 @@ extern "C" int vitmi_patch_im2col(int dtype, int B, int C, int S, int P, const f
 
 extern "C" int vitmi_tokens_assemble(int B, int np, int D, const float* tok, const float* cls,
                                      const float* pos, float* x, vitmi_stream_t stream) {
-  VITMI_CHECK_ARG(D % 4 == 0 && tok && x, "tokens_assemble: bad arguments");
+  VITMI_CHECK_ARG(B >= 0 && np >= 0 && D > 0, "tokens_assemble: need B >= 0, np >= 0 and D > 0 (got B = %d, np = %d, "
+                  "D = %d)", B, np, D);
+  VITMI_CHECK_ARG(D % 4 == 0 && tok && x, "tokens_assemble: bad arguments (D %% 4 == 0, tok and x not null)");
+  VITMI_CHECK_ARG(aligned_to(tok, 16) && aligned_to(cls, 16) && aligned_to(pos, 16) && aligned_to(x, 16),
+                  "tokens_assemble: tok, cls, pos and x must be 16-byte aligned");
+  if (B == 0) return VITMI_OK;
   const int64_t work = (int64_t)B * (np + 1) * D / 4;
   launch(tokens_assemble_kernel, dim3(grid_cap(work)), dim3(256), (hipStream_t)stream, no_stat, B, np, D, tok, cls,
          pos, x);
@@ -495,9 +507,15 @@ extern "C" int vitmi_tokens_assemble(int B, int np, int D, const float* tok, con
 extern "C" int vitmi_tokens_assemble_bwd(int B, int np, int D, const float* dx, float* dtok,
                                          void* dtok_lp, float* dcls, float* dpos,
                                          vitmi_stream_t stream) {
-  VITMI_CHECK_ARG(D % 4 == 0 && dx, "tokens_assemble_bwd: bad arguments");
+  VITMI_CHECK_ARG(B >= 0 && np >= 0 && D > 0, "tokens_assemble_bwd: need B >= 0, np >= 0 and D > 0 (got B = %d, "
+                  "np = %d, D = %d)", B, np, D);
+  VITMI_CHECK_ARG(D % 4 == 0 && dx, "tokens_assemble_bwd: bad arguments (D %% 4 == 0, dx not null)");
+  VITMI_CHECK_ARG(aligned_to(dx, 16) && aligned_to(dtok, 16) && aligned_to(dtok_lp, 8) && aligned_to(dcls, 16) &&
+                      aligned_to(dpos, 16),
+                  "tokens_assemble_bwd: dx, dtok, dcls and dpos must be 16-byte aligned, dtok_lp 8-byte aligned");
+  if (B == 0) return VITMI_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (dtok || dtok_lp) {
+  if ((dtok || dtok_lp) && np > 0) {
     const int64_t work = (int64_t)B * np * D / 4;
     launch(tokens_split_bwd_kernel, dim3(grid_cap(work)), dim3(256), s, no_stat, B, np, D, dx, dtok, (bf16*)dtok_lp);
   }
@@ -546,7 +564,8 @@ extern "C" int vitmi_bias_grad(int dtype, int64_t M, int64_t N, const void* dy, 
 
 extern "C" int vitmi_head_fwd(int B, int D, int C, const float* y, int64_t ldy, const float* w,
                               const float* b, float* logits, vitmi_stream_t stream) {
-  VITMI_CHECK_ARG(y && w && logits && B > 0 && C > 0, "head_fwd: bad arguments");
+  VITMI_CHECK_ARG(y && w && logits && B > 0 && C > 0, "head_fwd: bad arguments (null pointer, or B or C not positive)");
+  VITMI_CHECK_ARG(D > 0 && ldy >= D, "head_fwd: need D > 0 and ldy >= D (got D = %d, ldy = %lld)", D, (long long)ldy);
   const int waves = B * C;
   launch(head_fwd_kernel, dim3((waves + 3) / 4), dim3(256), (hipStream_t)stream, no_stat, B, D, C, y, ldy, w, b,
          logits);
@@ -557,7 +576,9 @@ extern "C" int vitmi_head_fwd(int B, int D, int C, const float* y, int64_t ldy, 
 extern "C" int vitmi_head_bwd(int B, int D, int C, const float* dlogits, const float* y, int64_t ldy,
                               const float* w, float* dy, float* dw, float* db,
                               vitmi_stream_t stream) {
-  VITMI_CHECK_ARG(dlogits && y && w && dy && dw, "head_bwd: bad arguments");
+  VITMI_CHECK_ARG(dlogits && y && w && dy && dw, "head_bwd: bad arguments (null pointer)");
+  VITMI_CHECK_ARG(B > 0 && C > 0, "head_bwd: need B > 0 and C > 0 (got B = %d, C = %d)", B, C);
+  VITMI_CHECK_ARG(D > 0 && ldy >= D, "head_bwd: need D > 0 and ldy >= D (got D = %d, ldy = %lld)", D, (long long)ldy);
   VITMI_CHECK_ARG(C <= 65535, "head_bwd: at most 65535 classes");
   hipStream_t s = (hipStream_t)stream;
   launch(head_bwd_dy_kernel, dim3((unsigned)(((int64_t)B * D + 255) / 256)), dim3(256), s, no_stat, B, D, C, dlogits,
@@ -578,6 +599,7 @@ extern "C" int vitmi_loss_fwd_bwd(int kind, int B, int C, const float* logits, c
 }
 
 extern "C" int vitmi_cast_f32_bf16(int64_t n, const float* src, void* dst, vitmi_stream_t stream) {
+  VITMI_CHECK_ARG(n >= 0, "cast: n must be >= 0 (got %lld)", (long long)n);
   VITMI_CHECK_ARG(src && dst, "cast: null pointer");
   VITMI_CHECK_ARG(aligned_to(src, 16) && aligned_to(dst, 16), "cast: 16-byte alignment required");
   if (n == 0) return VITMI_OK;
@@ -587,6 +609,7 @@ extern "C" int vitmi_cast_f32_bf16(int64_t n, const float* src, void* dst, vitmi
 }
 
 extern "C" int vitmi_cast_bf16_f32(int64_t n, const void* src, float* dst, vitmi_stream_t stream) {
+  VITMI_CHECK_ARG(n >= 0, "cast_bf16_f32: n must be >= 0 (got %lld)", (long long)n);
   VITMI_CHECK_ARG(src && dst, "cast_bf16_f32: null pointer");
   VITMI_CHECK_ARG(aligned_to(src, 16) && aligned_to(dst, 16), "cast_bf16_f32: 16-byte alignment required");
   if (n == 0) return VITMI_OK;
@@ -600,6 +623,7 @@ extern "C" int vitmi_dropout_apply(int64_t M, int64_t N, const float* x, int64_t
                                    uint32_t thresh, float scale, vitmi_stream_t stream) {
   VITMI_CHECK_ARG(x && y, "dropout_apply: null pointer");
   VITMI_CHECK_ARG(y_dtype == VITMI_F32 || y_dtype == VITMI_BF16, "dropout_apply: bad dtype %d", y_dtype);
+  VITMI_CHECK_ARG(M >= 0 && N >= 0, "dropout_apply: negative size (M = %lld, N = %lld)", (long long)M, (long long)N);
   VITMI_CHECK_ARG(N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= N && ldy >= N,
                   "dropout_apply: N and leading dims must be multiples of 4");
   VITMI_CHECK_ARG(aligned_to(x, 16) && aligned_to(y, 8), "dropout_apply: alignment");
