@@ -213,6 +213,38 @@ int vitmi_layernorm_bwd(int64_t M, int D, const void* dy, int dy_dtype, int64_t 
                         float* dxsum, void* workspace, size_t ws_bytes, vitmi_stream_t stream);
 size_t vitmi_layernorm_bwd_workspace_size(int64_t M, int D);
 /* ---------------------------------------------------------------------------
+ * QK-norm: LayerNorm over the head dimension of the queries and keys before QK^T (ViT-22B; timm's
+ * qk_norm=True with norm_layer=LayerNorm, blocks.i.attn.q_norm / k_norm).  qkv is [M][ld >= 3*H*dh] of
+ * dtype (VITMI_F32 or VITMI_BF16) in the attention layout (q | k | v column blocks, head h at h*dh),
+ * dh = 64, 1 <= H <= 32.  gamma_* / beta_* are fp32 [dh], one pair for q and one for k, shared by all
+ * heads.  mean / rstd are fp32 [M][2H]: column j < H is q head j, column H + j is k head j.
+ *
+ * vitmi_qknorm_fwd: out [M][ldo >= 3*H*dh] (same dtype) gets LN(q head; gamma_q, beta_q, eps) and
+ *   LN(k head; gamma_k, beta_k, eps) -- mean, variance about the computed mean, rsqrtf, (x - mu) * rs *
+ *   g + b in fp32, one round-to-nearest store -- and the v block bit for bit, so the attention entry
+ *   points take `out` unchanged.  out must not alias qkv: the backward reads the pre-norm values.
+ * vitmi_qknorm_bwd: qkv is the forward's INPUT (pre-norm), mean / rstd its statistics.  dqkv [M][ldd]
+ *   arrives holding the gradient of `out` (the attention backward's output); its q and k blocks are
+ *   replaced in place by rs * (gy - mean(gy) - xhat * mean(gy * xhat)), gy = dy * gamma, rounded once to
+ *   dtype; the v block is not written.  dgamma_* / dbeta_* [dh] += the sums over rows and heads of
+ *   dy * xhat / dy; dbias [3*H*dh] += the column sums of the finished dqkv (the qkv bias gradient: for q
+ *   and k the stored, rounded values, for v the columns as given).  Each of the five may be NULL.  The
+ *   sums are per-thread and per-block partials in the workspace (>= vitmi_qknorm_bwd_workspace_size(M,
+ *   H) bytes, either dtype) finished by the fixed-order fold (queued between vitmi_fold_begin and
+ *   vitmi_fold_end): no atomics, bitwise reproducible.
+ * Preconditions (VITMI_ERR_INVALID otherwise, nothing launched): dtype one of the two; dh == 64; H in
+ * [1, 32]; ld, ldo, ldd >= 3*H*dh and multiples of 8 (bf16) / 4 (fp32); qkv, out, dqkv, gamma, beta and
+ * the workspace 16-byte aligned (every access is a 16-byte vector); no required pointer NULL; out !=
+ * qkv; the workspace large enough.  M == 0 returns VITMI_OK and writes nothing. */
+int vitmi_qknorm_fwd(int dtype, int64_t M, int H, int dh, const void* qkv, int64_t ld,
+                     const float* gamma_q, const float* beta_q, const float* gamma_k, const float* beta_k,
+                     float eps, void* out, int64_t ldo, float* mean, float* rstd, vitmi_stream_t stream);
+size_t vitmi_qknorm_bwd_workspace_size(int64_t M, int H);
+int vitmi_qknorm_bwd(int dtype, int64_t M, int H, int dh, const void* qkv, int64_t ld,
+                     const float* mean, const float* rstd, const float* gamma_q, const float* gamma_k,
+                     void* dqkv, int64_t ldd, float* dgamma_q, float* dbeta_q, float* dgamma_k, float* dbeta_k,
+                     float* dbias, void* workspace, size_t ws_bytes, vitmi_stream_t stream);
+/* ---------------------------------------------------------------------------
  * Multi-head scaled-dot-product attention (layers.MultiHeadAttention called (q, v, k),
  * models/CvT(Par).py:137,185; einsum-softmax-einsum old_codes/MS_CvT.py:202-207).
  * qkv: [B*N][3*H*dh] token-major (q | k | v column blocks, head h at h*dh); o: [B*N][H*dh];

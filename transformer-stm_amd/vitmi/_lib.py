@@ -49,6 +49,9 @@ SIGNATURES = {
     "vitmi_layernorm_fwd": (I, [L, I, P, L, P, P, F, P, I, L, P, P, P]),
     "vitmi_layernorm_bwd": (I, [L, I, P, I, L, P, L, P, P, P, P, L, P, L, P, L, P, P, P, P, S, P]),
     "vitmi_layernorm_bwd_workspace_size": (S, [L, I]),
+    "vitmi_qknorm_fwd": (I, [I, L, I, I, P, L, P, P, P, P, F, P, L, P, P, P]),
+    "vitmi_qknorm_bwd_workspace_size": (S, [L, I]),
+    "vitmi_qknorm_bwd": (I, [I, L, I, I, P, L, P, P, P, P, P, L, P, P, P, P, P, P, S, P]),
     "vitmi_attention_fwd": (I, [I, I, I, I, I, F, P, P, P, P]),
     "vitmi_attention_fwd_x3": (I, [I, I, I, I, F, P, P, P, P, P]),
     "vitmi_attention_fwd_f8": (I, [I, I, I, I, F, P, P, P, P, P]),

@@ -75,6 +75,11 @@ class ViTConfig:
     # and eval).  None = off: no such parameters.  Any finite float is a scale, 0.0 included (a
     # ReZero-style start); timm treats a falsy value as off, vitmi does not.
     init_values: "float | None" = None
+    # QK-norm (ViT-22B; timm's qk_norm=True): a LayerNorm (epsilon ln_eps) over the head dimension of the
+    # queries and of the keys before QK^T, parameters blocks.i.attn.q_norm / k_norm (.weight, .bias,
+    # [head_dim], shared by all heads, ones / zeros).  Part of the model (the same in train and eval).
+    # False = off: no such parameters and no launch.
+    qk_norm: bool = False
 
     def __post_init__(self):
         if self.init_values is not None and not math.isfinite(self.init_values):

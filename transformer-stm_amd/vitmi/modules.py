@@ -9,7 +9,8 @@ CvT (``old_codes/MS_CvT.py``: ``Mlp`` :53, ``Attention`` :77, ``Block`` :289,
     VisionTransformer(cfg)
       patch_embed: ConvEmbed      (.proj Conv2d-shaped params, optional .norm)
       cls_token, pos_embed
-      blocks[i]: Block            (.norm1, .attn: Attention(.qkv, .proj), .norm2, .mlp: Mlp(.fc1, .fc2))
+      blocks[i]: Block            (.norm1, .attn: Attention(.qkv, .proj[, .q_norm, .k_norm]), .norm2,
+                                   .mlp: Mlp(.fc1, .fc2))
       norm: LayerNorm, head: Linear
 
 Every forward and backward runs the hand-written gfx950 kernels of libvitmi.so
@@ -140,6 +141,34 @@ def _proj_bwd(g: Tensor, o: Tensor, wo: Tensor, dw, db, wgrad) -> Tensor:
     if db is not None:
         ops.bias_grad(g, db)
     return do
+
+
+def _qk_fwd(attn, qkv: Tensor):
+    """QK-norm between the qkv GEMM and attention (``attn.q_norm`` / ``k_norm``; include/vitmi.h,
+    "QK-norm"): (the attention operand, what the backward needs besides it).  Without QK-norm: (qkv, ())
+    and no launch.  With it the attention operand is the normalised buffer, and the pre-norm buffer and
+    the statistics are saved as well: one extra [M, 3D] activation per block."""
+    if attn.q_norm is None:
+        return qkv, ()
+    qn, kn = attn.q_norm, attn.k_norm
+    out, qm, qr = ops.qknorm_fwd(qkv, attn.num_heads, qn.weight, qn.bias, kn.weight, kn.bias, qn.eps)
+    return out, (qkv, qm, qr)
+
+
+def _qk_bwd(attn, gs, qkv: Tensor, o: Tensor, do: Tensor, lse: Tensor, B: int, N: int, qk) -> Tensor:
+    """The attention backward from ``qkv``, the operand the forward's attention took, and ``qk``
+    (_qk_fwd's extras): dqkv, the gradient of the qkv GEMM's output, with the qkv bias gradient formed on
+    the way.  Without QK-norm that is the column sums of the attention backward's output, fused into
+    its kernels.  With it those sums are the gradient of a bias added AFTER the norm for the q and k
+    columns, so the attention backward runs without them and vitmi_qknorm_bwd, which turns the q and k
+    blocks of dqkv into the pre-norm gradient in place, sums the finished columns."""
+    if not qk:
+        return ops.attention_bwd(qkv, o, do, lse, B, N, attn.num_heads, attn.scale, bias_grad=gs(attn.qkv.bias))
+    pre, qm, qr = qk
+    qn, kn = attn.q_norm, attn.k_norm
+    dqkv = ops.attention_bwd(qkv, o, do, lse, B, N, attn.num_heads, attn.scale)
+    return ops.qknorm_bwd(pre, qm, qr, qn.weight, kn.weight, dqkv, gs(qn.weight), gs(qn.bias), gs(kn.weight),
+                          gs(kn.bias), gs(attn.qkv.bias))
 
 
 def _sink(ctx, first: int, params, arena=None, extra=()) -> GradSink:
@@ -279,10 +308,12 @@ class _LinearFn(torch.autograd.Function):
 class Attention(nn.Module):
     """ConvAttention with identity ('linear') projections (models/CvT(Par).py:115-191):
     fused Q/K/V linear [D -> 3D], softmax(QK^T * scale) V, out-projection.
-    ``forward(x, h, w)`` mirrors old_codes/MS_CvT.py:190 (h, w unused for 'linear')."""
+    ``forward(x, h, w)`` mirrors old_codes/MS_CvT.py:190 (h, w unused for 'linear').
+    ``qk_norm=True``: a LayerNorm (epsilon ``eps``) over each head's 64 columns of q and of k before
+    QK^T, parameters ``q_norm`` / ``k_norm`` shared by all heads (timm's ``qk_norm=True``)."""
 
     def __init__(self, dim: int, num_heads: int, qkv_bias: bool = True, attn_scale: str = "head",
-                 dtype: str = "bf16"):
+                 dtype: str = "bf16", qk_norm: bool = False, eps: float = 1e-6):
         super().__init__()
         if dim % num_heads or dim // num_heads != 64:
             raise ValueError("vitmi Attention needs head_dim == 64")
@@ -291,13 +322,19 @@ class Attention(nn.Module):
         self.qkv = Linear(dim, 3 * dim, bias=qkv_bias)
         self.proj = Linear(dim, dim)
         self.dtype = dtype
+        # after qkv and proj: the parameter order without QK-norm is a prefix of this one
+        self.q_norm = LayerNorm(dim // num_heads, eps) if qk_norm else None
+        self.k_norm = LayerNorm(dim // num_heads, eps) if qk_norm else None
 
     def forward(self, x: Tensor, h: Optional[int] = None, w: Optional[int] = None) -> Tensor:
         _check_cuda(x)
         return _AttentionFn.apply(x, self, *self._params())
 
     def _params(self):
-        return [p for p in (self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias) if p is not None]
+        ps = [self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias]
+        if self.q_norm is not None:
+            ps += [self.q_norm.weight, self.q_norm.bias, self.k_norm.weight, self.k_norm.bias]
+        return [p for p in ps if p is not None]
 
 
 class _AttentionFn(torch.autograd.Function):
@@ -308,17 +345,17 @@ class _AttentionFn(torch.autograd.Function):
         x2 = x.contiguous().float().view(B * N, D)
         xo = x2 if T == F32 else ops.cast_bf16(x2)
         wq, wo = _lp(mod, mod.qkv.weight, T), _lp(mod, mod.proj.weight, T)
-        qkv = ops.linear_fwd(xo, wq, mod.qkv.bias, T)
+        qkv, qk = _qk_fwd(mod, ops.linear_fwd(xo, wq, mod.qkv.bias, T))
         o, lse = ops.attention_fwd(qkv, B, N, mod.num_heads, mod.scale)
         y = ops.linear_fwd(o, wo, mod.proj.bias, F32)
-        ctx.save_for_backward(xo, qkv, o, lse, wq, wo)
+        ctx.save_for_backward(xo, qkv, o, lse, wq, wo, *qk)
         ctx.mod, ctx.shape = mod, (B, N, D)
         return y.view(B, N, D)
 
     @staticmethod
     @_folds
     def backward(ctx, dy):
-        xo, qkv, o, lse, wq, wo = ctx.saved_tensors
+        xo, qkv, o, lse, wq, wo, *qk = ctx.saved_tensors
         mod, (B, N, D) = ctx.mod, ctx.shape
         ps = mod._params()
         gs = _sink(ctx, 2, ps, getattr(mod, "_arena", None))
@@ -326,7 +363,7 @@ class _AttentionFn(torch.autograd.Function):
         g = dy.contiguous().float().view(B * N, D)
         g_lp = _take_lp(g, T, dy)
         do = _proj_bwd(g_lp, o, wo, gs(mod.proj.weight), gs(mod.proj.bias), ops.linear_wgrad)
-        dqkv = ops.attention_bwd(qkv, o, do, lse, B, N, mod.num_heads, mod.scale, bias_grad=gs(mod.qkv.bias))
+        dqkv = _qk_bwd(mod, gs, qkv, o, do, lse, B, N, qk)
         dx = ops.linear_dgrad(dqkv, wq, F32)
         if gs.wants(mod.qkv.weight):
             ops.linear_wgrad(dqkv, xo, gs(mod.qkv.weight))
@@ -478,14 +515,15 @@ class Block(nn.Module):
     ``init_values`` (None: off): LayerScale, ``x += ls1.gamma * Attn(LN1(x)); x += ls2.gamma *
     MLP(LN2(x))`` with both gammas initialised to it (timm's ``init_values=``; any finite float, 0.0
     included, is a scale).  The gammas are folded into the out-projection's and fc2's weight operands
-    (include/vitmi.h, "LayerScale"); ``ls1`` / ``ls2`` come last in ``parameters()``."""
+    (include/vitmi.h, "LayerScale"); ``ls1`` / ``ls2`` come last in ``parameters()``.
+    ``qk_norm=True``: ``attn.q_norm`` / ``attn.k_norm`` (Attention), epsilon ``eps``."""
 
     def __init__(self, dim: int, num_heads: int, mlp_ratio: float = 4.0, qkv_bias: bool = True,
                  eps: float = 1e-6, attn_scale: str = "head", tie_norms: bool = False, dtype: str = "bf16",
-                 init_values: Optional[float] = None):
+                 init_values: Optional[float] = None, qk_norm: bool = False):
         super().__init__()
         self.norm1 = LayerNorm(dim, eps)
-        self.attn = Attention(dim, num_heads, qkv_bias, attn_scale, dtype)
+        self.attn = Attention(dim, num_heads, qkv_bias, attn_scale, dtype, qk_norm, eps)
         self.tie_norms = tie_norms
         if not tie_norms:
             self.norm2 = LayerNorm(dim, eps)
@@ -570,13 +608,13 @@ class _BlockFn(torch.autograd.Function):
             out = _BlockFn._forward_x3(ctx, x2, blk, B, N, D, H, drop, (wq, wo, w1, w2), bo, b2)
             return out.view(B, N, D)
         h1, m1, r1 = ops.layernorm_fwd(x2, n1.weight, n1.bias, blk.eps, T)
-        qkv = ops.linear_fwd(h1, wq, a_.qkv.bias, T)
+        qkv, qk = _qk_fwd(a_, ops.linear_fwd(h1, wq, a_.qkv.bias, T))
         o, lse = ops.attention_fwd(qkv, B, N, H, a_.scale)
         dr, dp = _branch_masks(drop, N)
         x1 = ops.linear_fwd(o, wo, bo, F32, ops.EPI_RESIDUAL, residual=x2, dropout=dr[0], droppath=dp[0])
         h2, m2, r2 = ops.layernorm_fwd(x1, n2.weight, n2.bias, blk.eps, T)
         out, act, u = _mlp_fwd(h2, w1, blk.mlp.fc1.bias, w2, b2, T, x1, dr[1:], dp[1])
-        ctx.save_for_backward(x2, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, u, act, wq, wo, w1, w2)
+        ctx.save_for_backward(x2, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, u, act, wq, wo, w1, w2, *qk)
         return out.view(B, N, D)
 
     @staticmethod
@@ -626,8 +664,13 @@ class _BlockFn(torch.autograd.Function):
         # the qkv GEMM's operands: split, weight-side split, or plain bf16 (h1 and the weight's bf16 shadow)
         qa, qw, qf8 = ((h1_3, w3(a_.qkv.weight), f8) if sq else (h1_3, split_w[id(a_.qkv.weight)], "w") if wq8
                        else (h1_3, wlp[0], False))
+        qk = ()
+        if a_.q_norm is not None and N > ops.ATTN_SEQ_MAX:
+            raise ValueError(f"vitmi: qk_norm with dtype '{blk.dtype}' needs a sequence of at most "
+                             f"{ops.ATTN_SEQ_MAX} tokens (got {N}): the streamed two-forward attention path of "
+                             "the precision knobs has no QK-norm")
         if N <= ops.ATTN_SEQ_MAX:   # q, k, v leave the GEMM epilogue in bf16
-            qkv = ops.linear_fwd(qa, qw, a_.qkv.bias, torch.bfloat16, f8=qf8)
+            qkv, qk = _qk_fwd(a_, ops.linear_fwd(qa, qw, a_.qkv.bias, torch.bfloat16, f8=qf8))
             o, o3, lse = (ops.attention_fwd_f8 if f8 else ops.attention_fwd_x3)(qkv, B, N, H, a_.scale)
         else:   # streamed kernels (N > 256): O from the fp32 kernel, o / lse from the bf16 one
             qkvf = ops.linear_fwd(qa, qw, a_.qkv.bias, F32, f8=qf8)
@@ -647,13 +690,13 @@ class _BlockFn(torch.autograd.Function):
         out = ops.linear_fwd(act3, w3(mlp.fc2.weight), b2, F32, ops.EPI_RESIDUAL, residual=x1, f8=f8)
         # the bf16 backward's operands: hi parts of the split activations (row-strided views)
         h1, h2, act = (h1_3[:, :D] if sq or wq8 else h1_3), h2_3[:, :D], act3[:, :mlp.fc1.weight.shape[0]]
-        ctx.save_for_backward(x2, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, dg, act, *wlp)
+        ctx.save_for_backward(x2, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, dg, act, *wlp, *qk)
         return out
 
     @staticmethod
     @_folds
     def backward(ctx, dout):
-        (x2, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, u, act, wq, wo, w1, w2) = ctx.saved_tensors
+        (x2, h1, m1, r1, qkv, o, lse, x1, h2, m2, r2, u, act, wq, wo, w1, w2, *qk) = ctx.saved_tensors
         blk, (B, N, D) = ctx.blk, ctx.shape
         M = B * N
         T = h1.dtype
@@ -707,8 +750,9 @@ class _BlockFn(torch.autograd.Function):
                 ops.bias_grad(dx1_lp, dbo)
         # (the out-projection's bias gradient is formed above either way)
         do = _proj_bwd(dx1_lp, o, wo, dwo, None, lambda *item: attn_wg.append(item))
-        # the qkv bias gradient (column sums of dqkv) comes out of the attention backward kernels
-        dqkv = ops.attention_bwd(qkv, o, do, lse, B, N, a_.num_heads, a_.scale, bias_grad=gs(a_.qkv.bias))
+        # the qkv bias gradient (column sums of dqkv) comes out of the attention backward kernels or,
+        # with QK-norm, out of its backward
+        dqkv = _qk_bwd(a_, gs, qkv, o, do, lse, B, N, qk)
         dh1 = ops.linear_dgrad(dqkv, wq, T)
         if gs.wants(a_.qkv.weight):
             attn_wg.append((dqkv, h1, gs(a_.qkv.weight)))
@@ -1094,7 +1138,7 @@ class VisionTransformer(nn.Module):
         self.pos_embed = nn.Parameter(torch.zeros(1, cfg.seq_len, D)) if cfg.pos_embed else None
         self.blocks = nn.ModuleList([
             Block(D, cfg.num_heads, cfg.mlp_ratio, cfg.qkv_bias, cfg.ln_eps, cfg.attn_scale, cfg.tie_norms,
-                  cfg.dtype, cfg.init_values) for _ in range(cfg.depth)])
+                  cfg.dtype, cfg.init_values, cfg.qk_norm) for _ in range(cfg.depth)])
         if cfg.split_qkv is not None:
             for blk in self.blocks:
                 blk.split_qkv = cfg.split_qkv

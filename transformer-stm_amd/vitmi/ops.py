@@ -448,6 +448,39 @@ def layernorm_bwd(dy: Tensor, x: Tensor, mean: Tensor, rstd: Tensor, w: Tensor,
     return dx, dx_lp
 
 
+# ---------------------------------------------------------------- QK-norm
+def qknorm_fwd(qkv: Tensor, H: int, gq: Tensor, bq: Tensor, gk: Tensor, bk: Tensor, eps: float):
+    """qkv [M, 3*H*64] (fp32 or bf16; rows may be strided) -> (out [M, 3*H*64] contiguous: LayerNorm of
+    every q and k head over its 64 columns, v bit for bit; mean, rstd fp32 [M, 2H])."""
+    M, ld = _rows(qkv)
+    W = qkv.shape[-1]
+    out = torch.empty(M, W, dtype=qkv.dtype, device=qkv.device)
+    mean = torch.empty(M, 2 * H, dtype=torch.float32, device=qkv.device)
+    rstd = torch.empty(M, 2 * H, dtype=torch.float32, device=qkv.device)
+    check(lib().vitmi_qknorm_fwd(dt(qkv.dtype), M, H, W // (3 * H), _p(qkv), ld, _p(gq), _p(bq), _p(gk), _p(bk),
+                                 float(eps), _p(out), W, _p(mean), _p(rstd), _s()), "qknorm_fwd")
+    return out, mean, rstd
+
+
+def qknorm_bwd(qkv: Tensor, mean: Tensor, rstd: Tensor, gq: Tensor, gk: Tensor, dqkv: Tensor,
+               dgq: Optional[Tensor], dbq: Optional[Tensor], dgk: Optional[Tensor], dbk: Optional[Tensor],
+               dbias: Optional[Tensor]) -> Tensor:
+    """The backward of qknorm_fwd from its INPUT ``qkv`` and statistics.  ``dqkv`` holds the gradient of
+    the normalised buffer and is MODIFIED: its q and k blocks become the gradient of ``qkv``, v stays.
+    dgq / dbq / dgk / dbk (fp32 [64]) += the norm parameters' gradients, dbias (fp32 [3*H*64]) += the
+    column sums of the finished dqkv (the qkv bias gradient); each may be None.  Returns dqkv."""
+    M, ld = _rows(qkv)
+    _, ldd = _rows(dqkv)
+    W = qkv.shape[-1]
+    H = mean.shape[-1] // 2
+    assert dqkv.dtype == qkv.dtype and dqkv.shape[-1] == W
+    ws = _ws(lib().vitmi_qknorm_bwd_workspace_size(M, H), qkv)
+    check(lib().vitmi_qknorm_bwd(dt(qkv.dtype), M, H, W // (3 * H), _p(qkv), ld, _p(mean), _p(rstd), _p(gq), _p(gk),
+                                 _p(dqkv), ldd, _p(dgq), _p(dbq), _p(dgk), _p(dbk), _p(dbias), _p(ws), ws.numel(),
+                                 _s()), "qknorm_bwd")
+    return dqkv
+
+
 # ---------------------------------------------------------------- attention
 def attention_set_policy(policy: int) -> int:
     """0 = auto, 1 = always the streamed kernels, 2 = the whole-sequence 32-query forward / dQ
