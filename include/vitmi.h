@@ -668,6 +668,9 @@ int vitmi_ema_apply(int64_t n, float* p, float* ema, void* p_lp, int mode, vitmi
  *   Label values are not read on the host.  A label outside [0, C) matches no class: it keeps its
  *   weight in sum(t) but has no indexed logit and no gradient entry (row_loss = lse sum(q) minus the
  *   smoothing term alone), and the row is a miss.
+ *   Non-finite logits: nothing is hidden.  A row that holds a NaN logit, at any column and on either
+ *   load path, has row_loss[b] = NaN and every dlogits[b][c] = NaN, and loss[0] (and loss_sum) is NaN;
+ *   the other rows of the batch keep their bits.
  *   One wave64 per row, one online (max, sum) pass with 16-byte loads when C % 4 == 0, ldl (lds, lddl)
  *   % 4 == 0 and the bases are 16-byte aligned, scalar loads otherwise; the gradient leaves from
  *   registers for C <= 1024 and from a second (L2) pass above.  A row's results depend on that row

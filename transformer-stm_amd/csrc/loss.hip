@@ -94,9 +94,13 @@ __device__ __forceinline__ void xent_take(XentAcc& a, const float (&v)[W], const
     a.s *= expf(a.m - vm);
     a.m = vm;
   }
-  if (a.m != -INFINITY) {  // every element so far is -inf otherwise: nothing to add (and no inf - inf)
+  if (a.m != -INFINITY) {
 #pragma unroll
     for (int j = 0; j < W; ++j) a.s += expf(v[j] - a.m);
+  } else {                 // every element so far is -inf or NaN: -inf adds nothing (and forms no inf - inf),
+#pragma unroll             // a NaN (which no max rises for) goes into the sum and stays through every rescale
+    for (int j = 0; j < W; ++j)
+      if (v[j] != v[j]) a.s = v[j];
   }
 #pragma unroll
   for (int j = 0; j < W; ++j) {
@@ -161,7 +165,8 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(XentArgs p) {
 
   // combine the lanes
   const float M = wave_max(a.m);
-  const float se = wave_sum(a.m == -INFINITY ? 0.f : a.s * expf(a.m - M));
+  // a lane that met no finite element holds s = 0, or the NaN it met
+  const float se = wave_sum(a.m == -INFINITY ? a.s : a.s * expf(a.m - M));
   const float lse = M + logf(se);
   const int cnt = wave_sum_i(a.cnt);
 
